@@ -4,6 +4,13 @@
     python bench.py [--gpus N --steps K --warmup W]    (N > 1: starts its N ranks itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (same, launched)
     ... bench.py --gpus 8 --global-batch 1048576                 (BASELINE configs[3])
+    python bench.py --full ...       (also the legs reported beside the headline, see below)
+    python bench.py --dump-outputs DIR ...   (the last timed step's outputs as DIR/*.npy)
+
+A plain run sets up, warms up, times --steps steps and prints the line; everything measured
+beside the headline (the other path, floors, CPU baseline, Fp export, prover columns, hasher;
+N > 1: collectives alone, witness gathers, the config-4 leg) runs only with --full, and its
+fields are null without it.
 
 One step = witness fill + constraint eval of the whole per-GPU batch: --path fused (the
 headline) runs b2f_fill_eval_dev (record kernel + the fused kernel that checks every tile as it
@@ -205,6 +212,46 @@ def cpu_baseline(rounds, mix, target_s, threads):
     return out
 
 
+DUMP_H_ROWS = 1 << 18      # h' rows dumped at most (the 2^18 headline batch: all of them)
+DUMP_TRACE_ROWS = 1 << 17  # trace rows sampled
+DUMP_SEED = 0x5962be5d
+
+
+def dump_outputs(path, batch, torch):
+    """--dump-outputs: what the last timed step left in the batch's output buffers, the arrays a
+    caller of fill_evaluate (or fill + evaluate) receives, as float64 .npy files (every value
+    is a 32-bit word, so float64 holds it exactly; 64-bit words are split low word first):
+      h_out.npy       [rows, 16]  h' of instances h_out_rows.npy (all of them up to 2^18, else a
+                                  seeded sorted sample), 8 u64 as 16 u32 words
+      report.npy      [42]        the eval report's 21 u64 counters as u32 words
+      trace.npy       [11, S]     the 10 advice columns and the fixed column at the S seeded
+                                  sample rows trace_rows.npy (sorted, below used_rows)
+    The samples depend only on the batch's shape, so two builds run with the same arguments
+    dump the same cells: 33.6 + 11.5 MB at the headline size."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    dev = batch.advice.device
+
+    def words(t):
+        return t.contiguous().cpu().numpy().view(np.uint32).astype(np.float64)
+
+    if batch.n <= DUMP_H_ROWS:
+        inst = np.arange(batch.n, dtype=np.int64)
+        h = batch.h_out
+    else:
+        inst = np.sort(rng.integers(0, batch.n, DUMP_H_ROWS, dtype=np.int64))
+        h = batch.h_out[torch.from_numpy(inst).to(dev)]
+    rows = np.sort(rng.integers(0, batch.used_rows, min(DUMP_TRACE_ROWS, batch.used_rows),
+                                dtype=np.int64))
+    idx = torch.from_numpy(rows).to(dev)
+    trace = torch.cat([batch.advice[:, idx], batch.fixed[idx].unsqueeze(0)])
+    np.save(os.path.join(path, "h_out.npy"), words(h))
+    np.save(os.path.join(path, "h_out_rows.npy"), inst.astype(np.float64))
+    np.save(os.path.join(path, "report.npy"), words(batch.report))
+    np.save(os.path.join(path, "trace.npy"), words(trace))
+    np.save(os.path.join(path, "trace_rows.npy"), rows.astype(np.float64))
+
+
 def free_port():
     import socket
 
@@ -335,6 +382,14 @@ def main():
                     help="interleaved reps of the floor variants and product kernels (0 = skip)")
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
                     help="PMC-derived HBM bytes per launch (tools/pmc_traffic.py output)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs reported beside it (CPU baseline, "
+                         "floors, the other path, Fp export, lookup and permutation columns, "
+                         "hasher; N > 1: collectives alone, witness gathers, the config-4 leg). "
+                         "Without it their fields are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left (h', the "
+                         "report, a seeded sample of trace rows; rank 0's) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -542,6 +597,8 @@ def main():
     elapsed, ktimes, rep = timed_loop(batch, info, args.path, args.steps, args.warmup, global_n)
     value = total_n * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch, torch)
 
     # roofline: algorithmic bytes per launch / average launch duration (HIP events)
     n = n_local
@@ -603,11 +660,11 @@ def main():
     # N > 1: the legs after the headline use collectives; one that hangs (a rank failing where
     # the others wait) must not cost the headline line, so a watchdog prints it and ends every
     # rank once the extras run past --extras-timeout (ExtrasWatchdog)
-    watchdog = ExtrasWatchdog(args.extras_timeout if dist_on else 0, rank, headline)
+    watchdog = ExtrasWatchdog(args.extras_timeout if dist_on and args.full else 0, rank, headline)
 
     collectives = None
     witness = None
-    if dist_on:
+    if dist_on and args.full:
         collectives = collectives_alone(batch, info, args.steps)
         if global_n:
             witness = witness_gather(batch.advice, batch.fixed, info["rows"],
@@ -639,7 +696,7 @@ def main():
     # (fill floor, fused pass, split fill, eval floor, split eval), so drifts in the box's
     # store rate hit both sides alike; min and median over the reps are reported.
     floors = None
-    if solo and args.floor_reps > 0:
+    if args.full and solo and args.floor_reps > 0:
         try:
             deng = b2f.Engine(local, diag=True)
             samples = {"fill_floor": [], "stream_floor": [], "fill_eval": [], "fill": [],
@@ -693,7 +750,7 @@ def main():
     # the other path, timed the same way (reported beside the headline, not part of it)
     aux = None
     other = "fused" if args.path == "split" else "split"
-    if args.aux_steps > 0 and solo:
+    if args.full and args.aux_steps > 0 and solo:
         run_path(batch, other)
         eng.sync(stream)
         eng.set_timing(True)
@@ -714,7 +771,7 @@ def main():
     # Montgomery pallas limbs for a chunk of the resident trace (4 B read, 32 B written/cell)
     fp_export = None
     fp_export_bn254 = None
-    if args.export_rows > 0 and solo:
+    if args.full and args.export_rows > 0 and solo:
         nr = min(args.export_rows, batch.total_rows)
         out = torch.empty((10, nr, 4), dtype=torch.int64, device=batch.advice.device)
         res = {}
@@ -739,7 +796,7 @@ def main():
     # Lookup-argument prover columns for circuits cut from the resident
     # trace, and the multi-block hasher (row 3): reported beside the headline, not part of it
     lookup = None
-    if solo and args.lookup_circuits > 0:
+    if args.full and solo and args.lookup_circuits > 0:
         try:
             usable = (1 << 17) - 7
             nc = min(args.lookup_circuits, batch.total_rows // usable)
@@ -784,7 +841,7 @@ def main():
     # Permutation-argument prover columns of a 2^k-row circuit cut from
     # the resident trace: sigma (8 columns) + the grand products of ceil(8 / 3) column sets
     perm = None
-    if solo and args.perm_k > 0:
+    if args.full and solo and args.perm_k > 0:
         try:
             k = args.perm_k
             usable = (1 << k) - 7
@@ -849,7 +906,7 @@ def main():
         except Exception as e:  # reported, never masks the headline
             perm = {"error": repr(e)}
     hasher_aux = None
-    if solo and args.hasher_messages > 0:
+    if args.full and solo and args.hasher_messages > 0:
         try:
             import hashlib
 
@@ -884,7 +941,7 @@ def main():
     # the ranks, fill + eval timed the same way, then the whole witness table gathered
     # (--config4-world 2 --config4 32768 rehearses the same code on a one-GPU box)
     config4 = None
-    if dist_on and world == args.config4_world and not global_n and args.config4 > 0:
+    if args.full and dist_on and world == args.config4_world and not global_n and args.config4 > 0:
         try:
             del batch
             torch.cuda.empty_cache()
@@ -904,7 +961,7 @@ def main():
             config4["hbm_free_after_gb"] = round(torch.cuda.mem_get_info(local)[0] / 1e9, 1)
 
     cpu = None
-    if rank == 0 and solo and not args.no_cpu:
+    if args.full and rank == 0 and solo and not args.no_cpu:
         cpu = cpu_baseline(args.rounds, mix, args.cpu_seconds, args.cpu_threads)
 
     out = headline()

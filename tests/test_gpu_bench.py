@@ -19,7 +19,7 @@ def test_bench_line_config_is_the_headline_batch(extra, rounds_of):
 
     n = 64
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(n), "--steps", "2",
-           "--warmup", "1", "--no-cpu", "--perm-k", "14", "--lookup-circuits", "1",
+           "--warmup", "1", "--full", "--no-cpu", "--perm-k", "14", "--lookup-circuits", "1",
            "--hasher-messages", "64", "--floor-reps", "2", "--aux-steps", "1",
            "--export-rows", "4096"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
@@ -51,6 +51,53 @@ def test_bench_line_config_is_the_headline_batch(extra, rounds_of):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(orc, tmp_path):
+    """Without --full the line carries the headline and none of the legs beside it, --steps is
+    the number of timed steps, and --dump-outputs writes what the last timed step left: h', the
+    report and the sampled trace rows, here checked cell for cell against the oracle."""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "zk-odst_amd"))
+    from b2f import synth
+
+    n = 48
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", str(n),
+           "--steps", "3", "--warmup", "1", "--mix", "--dump-outputs", str(tmp_path / "dump")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["kernels"]["fill_eval"]["launches"] == 3
+    assert line["value"] > 0 and line["unit"] == "compressions/s" and line["dtype"] == "u32"
+    assert line["higher_is_better"] is True and line["roofline"]["bound"] == "hbm"
+    for k in ("cpu_baseline", "floors", "other_path", "fp_export", "fp_export_bn254",
+              "lookup_columns", "permutation_columns", "hasher", "collectives", "witness_gather",
+              "config4", "gpu_vs_cpu"):
+        assert line[k] is None, k
+
+    x = synth.batch(n, rounds=12, rounds_mix=[1, 4, 12])
+    ox = np.frombuffer(x.tobytes(), dtype=orc.INPUT_DTYPE).copy()
+    adv, fixed, h, off = orc.fill(ox)
+    d = {f[:-4]: np.load(str(tmp_path / "dump" / f)) for f in os.listdir(str(tmp_path / "dump"))}
+    assert set(d) == {"h_out", "h_out_rows", "report", "trace", "trace_rows"}
+    assert all(a.dtype == np.float64 for a in d.values())
+    assert sum(a.nbytes for a in d.values()) <= 64 * 10**6
+    assert np.array_equal(d["h_out_rows"], np.arange(n))
+    assert np.array_equal(d["h_out"], h.view(np.uint32).reshape(n, 16).astype(np.float64))
+    rows = d["trace_rows"].astype(np.int64)
+    assert len(rows) == min(1 << 17, int(off[-1])) and np.all(np.diff(rows) >= 0) and rows[-1] < int(off[-1])
+    assert np.array_equal(d["trace"][:10], adv[:, rows].astype(np.float64))
+    assert np.array_equal(d["trace"][10], fixed[rows].astype(np.float64))
+    rep = d["report"].astype(np.uint64)
+    rep = rep[0::2] | (rep[1::2] << np.uint64(32))
+    want = orc.evaluate(adv, fixed, off)
+    assert list(rep[:16]) == want["gate_failures"] and rep[18] == 2**64 - 1
+    assert rep[19] == want["rows_checked"] and rep[16] == rep[17] == rep[20] == 0
+
+
+@pytest.mark.gpu
 def test_bench_gpus2_spawns_two_ranks_without_launcher():
     """`bench.py --gpus 2` with no launcher runs two ranks by itself (here
     rehearsed on one GPU: B2F_BENCH_REHEARSE=1 puts both ranks on cuda:0 with gloo
@@ -61,7 +108,7 @@ def test_bench_gpus2_spawns_two_ranks_without_launcher():
     env["B2F_BENCH_REHEARSE"] = "1"
     n = 64
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", str(n),
-           "--steps", "2", "--warmup", "1", "--witness-gather", "32", "--extras-timeout", "120"]
+           "--steps", "2", "--warmup", "1", "--full", "--witness-gather", "32", "--extras-timeout", "120"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -84,7 +131,7 @@ def test_bench_rccl_code_path_one_rank():
                 "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29533"})
     env.pop("B2F_BENCH_REHEARSE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "4096", "--steps", "2",
-           "--warmup", "1", "--witness-gather", "64", "--config4", "16384", "--config4-world", "1",
+           "--warmup", "1", "--full", "--witness-gather", "64", "--config4", "16384", "--config4-world", "1",
            "--extras-timeout", "200"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -14,6 +14,6 @@ cd $R
 timeout -k 10 600 python3 -u -m pytest tests -m gpu -x -v --timeout 240 --timeout-method thread > $OUT/gpu_tests.txt 2>&1 || exit 1
 timeout -k 10 120 python3 -c 'import __graft_entry__ as g; g.smoke()' > $OUT/smoke.txt 2>&1 || exit 2
 bash tools/round_profile.sh $TAG || exit 3
-cd $R && B2F_BENCH_REHEARSE=1 timeout -k 10 300 python3 bench.py --gpus 2 --batch 16384 --steps 3 --warmup 1 \
+cd $R && B2F_BENCH_REHEARSE=1 timeout -k 10 300 python3 bench.py --gpus 2 --full --batch 16384 --steps 3 --warmup 1 \
   > $OUT/rehearse_spawn_n2.json 2> $OUT/rehearse_spawn_n2.err || exit 4
 echo done
