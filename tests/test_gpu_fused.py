@@ -15,10 +15,9 @@ import numpy as np
 import pytest
 
 from conftest import random_inputs
+from verdict_util import FIXED_COL, INIT_ROWS, NONE, ROUND_ROWS, oracle_window, rounds_of
 
 pytestmark = pytest.mark.gpu
-
-NONE = 2**64 - 1
 
 
 def _as_oracle(x, orc):
@@ -477,3 +476,91 @@ def test_max_rounds_instance(engine, orc):
     bad.evaluate(engine)
     engine.sync(_stream())
     assert bad.report_dict() == got
+
+
+EDGE_CHUNK = 8  # B2F_FUSED_EDGE_CHUNK: consecutive edge tiles per claim (csrc/b2f_fused.hip)
+
+
+def test_fused_edge_injection_across_claims(engine, orc):
+    """The fused launch's edge tiles (one per instance: its init and final regions; then the zero
+    rows as 64-quad tiles) are claimed 8 at a time from a counter. With more than 8 tiles per wave
+    of the launch (W = 12 waves per CU at most) some wave claims a second chunk, and n = 8 W + 101
+    makes the chunk that holds the last instances run on into the zero-row tiles. Faults injected
+    into init, final and zero rows of instances claimed first, across a chunk boundary, last, and
+    at random: the written trace differs from the clean one in exactly the injected cell, and
+    the fused verdict equals b2f_eval_dev's on the written trace and the oracle's (a window of
+    instances around the fault, re-based to the global row; the whole trace for the zero rows)."""
+    import b2f
+    import torch
+
+    W = 12 * torch.cuda.get_device_properties(0).multi_processor_count
+    n = EDGE_CHUNK * W + 101
+    assert n % EDGE_CHUNK != 0
+    x = random_inputs(n, (0, 0, 0, 1), 96)
+    used = int(b2f.offsets(x)[-1])
+    total = used + 4 * (64 * 3 + 5)
+    a = _fused(engine, x, total_rows=total)
+    rep = a.report_dict()
+    assert rep["first_failure"] == NONE and rep["rows_checked"] == total
+    cadv, cfix = a.advice.clone(), a.fixed.clone()
+    hadv, hfix = a.host_trace()  # host mirror of the clean trace, for the zero-row cases
+    hadv, hfix = hadv.copy(), hfix.copy()
+    off = a.offsets_host
+    assert rep == orc.evaluate(hadv, hfix, off)
+
+    def run(row, col, mask):
+        """One injected fused call over poisoned buffers; the written trace differs from the
+        clean one in exactly (col, row). Returns the fused report."""
+        a.advice.fill_(-1)
+        a.fixed.fill_(-1)
+        try:
+            engine.debug_inject(row, col, mask)
+            a.fill_evaluate(engine)
+            engine.sync(_stream())
+        finally:
+            engine.debug_inject(None)
+        got = a.report_dict()
+        dadv = (a.advice != cadv).nonzero().tolist()
+        dfix = (a.fixed != cfix).nonzero().reshape(-1).tolist()
+        if col < FIXED_COL:
+            assert dadv == [[col, row]] and dfix == [], (row, col, dadv[:4], dfix[:4])
+        else:
+            assert dadv == [] and dfix == [row], (row, col, dadv[:4], dfix[:4])
+        a.evaluate(engine)  # the standalone eval on the written trace
+        engine.sync(_stream())
+        ref = a.report_dict()
+        assert got == ref, (row, col, got, ref)
+        return got
+
+    rng = np.random.default_rng(96)
+    insts = [0, 7, 8, n - 102, n - 1] + [int(i) for i in rng.choice(n, 4, replace=False)]
+    flagged = cases = 0
+    for i in insts:
+        o_i = int(off[i])
+        row_f = o_i + INIT_ROWS + ROUND_ROWS * rounds_of(off, i)
+        for lo, hi in ((o_i, o_i + INIT_ROWS), (row_f, row_f + 64)):
+            for col in (0, 1, 2, FIXED_COL, int(rng.integers(3, 10))):
+                row = int(rng.integers(lo, hi))
+                got = run(row, col, 1 << int(rng.integers(0, 16)))
+                want = oracle_window(orc, a, i)
+                assert got == want, (i, row - o_i, col, got, want)
+                if col in (0, 1, 2, FIXED_COL):
+                    assert got["first_failure"] != NONE, (i, row - o_i, col)
+                flagged += got["first_failure"] != NONE
+                cases += 1
+    for row in (used, total - 1):
+        for col in (0, 1, 2, FIXED_COL, int(rng.integers(3, 10))):
+            mask = 1 << int(rng.integers(0, 16))
+            got = run(row, col, mask)
+            t = hfix if col == FIXED_COL else hadv[col]
+            t[row] ^= np.uint32(mask)
+            try:
+                want = orc.evaluate(hadv, hfix, off)
+            finally:
+                t[row] ^= np.uint32(mask)
+            assert got == want, (row - used, col, got, want)
+            if col in (0, 1, 2, FIXED_COL):
+                assert got["first_failure"] != NONE, (row - used, col)
+    assert 3 * flagged >= 2 * cases, (flagged, cases)
+    del cadv, cfix
+    torch.cuda.empty_cache()

@@ -2119,13 +2119,18 @@ __global__ void __launch_bounds__(256) eval_desc_kernel(const uint64_t* __restri
                        (uint32_t)__shfl((int)(uint32_t)r2, (int)(k + step) & 63, 64);
     if (k + step < 64 && v <= T) k += step;
   }
+  // both shuffles with every lane of the wave active: a shuffle reads 0 from a lane that has
+  // returned (T >= tiles) or sits in the other branch below (k == 63), and with many zero-round
+  // instances a lane's instance i0 + k lies further along the wave than its own tile (k > lane)
+  const uint64_t r0_sh = ((uint64_t)(uint32_t)__shfl((int)(r2 >> 32), (int)k, 64) << 32) |
+                         (uint32_t)__shfl((int)(uint32_t)r2, (int)k, 64);
   const uint64_t rn_sh = ((uint64_t)(uint32_t)__shfl((int)(r2 >> 32), (int)(k + 1) & 63, 64) << 32) |
                          (uint32_t)__shfl((int)(uint32_t)r2, (int)(k + 1) & 63, 64);
   if (T >= tiles) return;
   uint32_t i = i0 + k;
   uint64_t r0, r1;
   if (k < 63) {  // instance i0 + k and the next one are among the wave's 64
-    r0 = ((uint64_t)(uint32_t)__shfl((int)(r2 >> 32), (int)k, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)r2, (int)k, 64);
+    r0 = r0_sh;
     r1 = rn_sh;
   } else {  // past them
     i = search(T);
@@ -2304,61 +2309,66 @@ eval_hr_kernel(const uint32_t* __restrict__ adv, const uint32_t* __restrict__ fi
   uint32_t j = 0;
   const uint32_t cA0 = carry_addr(lane, lds_byte(S), 0), cA1 = carry_addr(lane, lds_byte(S), 1);
   auto raw_desc = [&](uint64_t tt) -> uint4 { return desc[tt].v; };
-  // per tile: its cells (lane = quad), its limb-table entry (the canonical dense / spread cell of
-  // state word lane / 4, limb lane % 4, as the half-round starts: gathered at a band's first tile
-  // and at an instance's first half-round, otherwise read from the previous tile's staging) and its
-  // message-copy source (message word SIGMA[..] limb, a_1 of its INW block), loaded one tile ahead
-  HCtx c = hctx(raw_desc(t < n_hr ? t : 0));
-  EvCells cur = ev_load(c, lane, lq, mg, mwh, mk, adv, fixed, total_rows, Sg, true);
-  while (t < n_hr) {
-    uint64_t tn = t + 1, bn = b;
-    uint32_t jn = j + 1;
-    if (jn == EV_BAND || tn >= n_hr) {
+  // A batch without half-round tiles (every instance has 0 rounds) has no descriptor: eval_desc_kernel
+  // wrote none, and desc[0] holds whatever the scratch held. No context is formed and no load
+  // issued from it; the wave goes straight to the edge walk.
+  if (n_hr != 0) {
+    // per tile: its cells (lane = quad), its limb-table entry (the canonical dense / spread cell of
+    // state word lane / 4, limb lane % 4, as the half-round starts: gathered at a band's first tile
+    // and at an instance's first half-round, otherwise read from the previous tile's staging) and its
+    // message-copy source (message word SIGMA[..] limb, a_1 of its INW block), loaded one tile ahead
+    HCtx c = hctx(raw_desc(t < n_hr ? t : 0));
+    EvCells cur = ev_load(c, lane, lq, mg, mwh, mk, adv, fixed, total_rows, Sg, true);
+    while (t < n_hr) {
+      uint64_t tn = t + 1, bn = b;
+      uint32_t jn = j + 1;
+      if (jn == EV_BAND || tn >= n_hr) {
 #if B2F_EVAL_DYN
-      bn = claim();
+        bn = claim();
 #else
-      bn = b + W;
+        bn = b + W;
 #endif
-      tn = bn * EV_BAND;
-      jn = 0;
+        tn = bn * EV_BAND;
+        jn = 0;
+      }
+      const HCtx cn = hctx(raw_desc(tn < n_hr ? tn : 0));
+      const EvCells nxt = ev_load(cn, lane, lq, mg, mwh, mk, adv, fixed, total_rows, Sg, jn == 0 || cn.hr == 0);
+      uint32_t ltd = cur.d, lts = cur.sp;
+      if (j != 0 && c.hr != 0) {  // the staging holds half-round hr - 1 of this instance
+        const uint32_t a = ((c.hr - 1) & 1u) ? cA1 : cA0;
+        ltd = ld32(a & 0xffffu);
+        lts = ld32(a >> 16);
+      }
+      asm volatile("" ::: "memory");  // read before the tile's cells overwrite the staging
+      if (qlane) {
+        uint4* q = reinterpret_cast<uint4*>(S + 4 * lane);
+        q[0 * HSTR / 4] = cur.c0;
+        q[1 * HSTR / 4] = cur.c1;
+        q[2 * HSTR / 4] = cur.c2;
+        q[3 * HSTR / 4] = cur.c3;
+        q[4 * HSTR / 4] = cur.c4;
+        q[5 * HSTR / 4] = cur.c5;
+        q[6 * HSTR / 4] = cur.c6;
+        q[7 * HSTR / 4] = cur.c7;
+        q[8 * HSTR / 4] = cur.c8;
+        q[9 * HSTR / 4] = cur.c9;
+        q[10 * HSTR / 4] = cur.c10;
+      }
+      S[H_LT + lane] = ltd;
+      S[H_LT + 64 + lane] = lts;
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+      const uint32_t mc = cur.mc;
+      const uint32_t acc = hr_fast_checks<MODE>(K, c.hr, [&] { return mc; });
+      if (__builtin_amdgcn_ballot_w64(acc != 0) && lane == 0) *dirty = 1u;
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+      c = cn;
+      cur = nxt;
+      t = tn;
+      j = jn;
+      b = bn;
     }
-    const HCtx cn = hctx(raw_desc(tn < n_hr ? tn : 0));
-    const EvCells nxt = ev_load(cn, lane, lq, mg, mwh, mk, adv, fixed, total_rows, Sg, jn == 0 || cn.hr == 0);
-    uint32_t ltd = cur.d, lts = cur.sp;
-    if (j != 0 && c.hr != 0) {  // the staging holds half-round hr - 1 of this instance
-      const uint32_t a = ((c.hr - 1) & 1u) ? cA1 : cA0;
-      ltd = ld32(a & 0xffffu);
-      lts = ld32(a >> 16);
-    }
-    asm volatile("" ::: "memory");  // read before the tile's cells overwrite the staging
-    if (qlane) {
-      uint4* q = reinterpret_cast<uint4*>(S + 4 * lane);
-      q[0 * HSTR / 4] = cur.c0;
-      q[1 * HSTR / 4] = cur.c1;
-      q[2 * HSTR / 4] = cur.c2;
-      q[3 * HSTR / 4] = cur.c3;
-      q[4 * HSTR / 4] = cur.c4;
-      q[5 * HSTR / 4] = cur.c5;
-      q[6 * HSTR / 4] = cur.c6;
-      q[7 * HSTR / 4] = cur.c7;
-      q[8 * HSTR / 4] = cur.c8;
-      q[9 * HSTR / 4] = cur.c9;
-      q[10 * HSTR / 4] = cur.c10;
-    }
-    S[H_LT + lane] = ltd;
-    S[H_LT + 64 + lane] = lts;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    const uint32_t mc = cur.mc;
-    const uint32_t acc = hr_fast_checks<MODE>(K, c.hr, [&] { return mc; });
-    if (__builtin_amdgcn_ballot_w64(acc != 0) && lane == 0) *dirty = 1u;
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    c = cn;
-    cur = nxt;
-    t = tn;
-    j = jn;
-    b = bn;
   }
   // then the edge tiles, in the wave's whole region (as the fused launch
   // does since round 4, the edge work fills this launch's tail instead of a launch after it)
@@ -2422,12 +2432,26 @@ constexpr uint32_t DEFER_CAP = 4096;
 
 namespace b2f {
 
-// Scratch of the fused path: tile descriptors for `tiles` instance tiles and the deferred row
-// list (count + DEFER_CAP rows).
+// Scratch of the fused path: tile descriptors for `tiles` instance tiles (written and read by the
+// eval's fast pass only) and the deferred row list (count + DEFER_CAP rows).
 // + the edge launch's redo list (count + one slot per instance; tiles >= instances)
+// + 16 bytes: the eval's band counter and dirty word (each with a spare word after it)
+// + 8 bytes: the fused half-round launch's instance counter and edge-tile counter
+// Every part has its own words: no call reads a word that only another kind of call writes.
+constexpr size_t SCRATCH_TAIL = 16 + 8;
 size_t fused_scratch_bytes(uint64_t tiles) {
-  // + the eval's band counter and dirty word
-  return tiles * sizeof(TileDesc) + 8 * (1 + DEFER_CAP) + 4 * (2 + tiles) + 16;
+  return tiles * sizeof(TileDesc) + 8 * (1 + DEFER_CAP) + 4 * (2 + tiles) + SCRATCH_TAIL;
+}
+// the scratch's last words, from its end: the fused launch's two counters, before them the eval's
+// dirty word (8 bytes) and band counter (8 bytes)
+static unsigned* scratch_fused_ctrs(void* scratch, uint64_t tiles) {
+  return reinterpret_cast<unsigned*>(reinterpret_cast<char*>(scratch) + fused_scratch_bytes(tiles) - 8);
+}
+static uint32_t* scratch_eval_dirty(void* scratch, uint64_t tiles) {
+  return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(scratch) + fused_scratch_bytes(tiles) - 16);
+}
+static unsigned* scratch_eval_bctr(void* scratch, uint64_t tiles) {
+  return reinterpret_cast<unsigned*>(reinterpret_cast<char*>(scratch) + fused_scratch_bytes(tiles) - 24);
 }
 
 // The eval's fast clean-check pass (see eval_hr_kernel) into the fused scratch; returns the
@@ -2439,8 +2463,8 @@ hipError_t launch_eval_fast(const uint32_t* d_adv, const uint32_t* d_fixed, cons
   mode = FZ_FULL;  // the product library runs the full pass only
 #endif
   TileDesc* desc = reinterpret_cast<TileDesc*>(scratch);
-  uint32_t* dirty = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(scratch) + fused_scratch_bytes(tiles) - 8);
-  unsigned* bctr = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(scratch) + fused_scratch_bytes(tiles) - 16);
+  uint32_t* dirty = scratch_eval_dirty(scratch, tiles);
+  unsigned* bctr = scratch_eval_bctr(scratch, tiles);
   hipError_t e = hipMemsetAsync(bctr, 0, 16, s);  // the band counter and the dirty word
   if (e != hipSuccess) return e;
   // tiles (an upper bound on the half-round tiles) >= 2 sum(rounds): every tile has its thread
@@ -2489,8 +2513,8 @@ uint64_t fused_instance_tiles(uint64_t total_rows, uint64_t n) {
   return (total_rows - (uint64_t)FIXED_ROWS * n) / 208 + 2 * n;
 }
 
-// Launch the fused path (b2f_fill_eval_dev) after the record kernel: tile descriptors, the
-// fused kernel, the deferred gates. `scratch` holds fused_scratch_bytes(tiles).
+// Launch the fused path (b2f_fill_eval_dev) after the record kernel: the fused kernel, the edge
+// redo, the deferred gates (no tile descriptors: that area of the scratch is the eval's). `scratch` holds fused_scratch_bytes(tiles).
 hipError_t launch_fill_eval(const b2f_input* d_in, uint32_t n, const uint64_t* d_off,
                             uint64_t total_rows, const uint64_t* rec, uint32_t* d_adv,
                             uint32_t* d_fixed, void* scratch, uint64_t tiles,
@@ -2501,9 +2525,9 @@ hipError_t launch_fill_eval(const b2f_input* d_in, uint32_t n, const uint64_t* d
   TileDesc* desc = reinterpret_cast<TileDesc*>(scratch);
   uint64_t* defer = reinterpret_cast<uint64_t*>(desc + tiles);
   uint32_t* redo = reinterpret_cast<uint32_t*>(defer + 1 + DEFER_CAP);
-  // the half-round launch's instance and edge-tile counters: the first two words of the
-  // tile-descriptor area (only the eval's fast pass uses descriptors)
-  unsigned* ictr = reinterpret_cast<unsigned*>(desc);
+  // the half-round launch's instance and edge-tile counters: their own two words at the scratch's
+  // end (the tile-descriptor area belongs to the eval's fast pass; this launch does not touch it)
+  unsigned* ictr = scratch_fused_ctrs(scratch, tiles);
   hipError_t e = hipMemsetAsync(defer, 0, 8, s);
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(ictr, 0, 8, s);  // the instance and the edge-tile counters

@@ -1394,8 +1394,8 @@ B2F_API int b2f_fill_dev(b2f_ctx* ctx, const b2f_input* d_in, size_t n, const ui
   return B2F_OK;
 }
 
-// The fused path's scratch (tile descriptors, deferred rows, redo list, the eval's dirty word),
-// grown on demand.
+// The fused path's scratch (the eval's tile descriptors, deferred rows, redo list, the eval's band
+// counter and dirty word, the fused launch's instance and edge-tile counters), grown on demand.
 static int ensure_fused_scratch(b2f_ctx* ctx, size_t need, hipStream_t s) {
   if (need > ctx->fz_cap) {
     HIPCHK(ctx, hipStreamSynchronize(s));
