@@ -85,3 +85,36 @@ def test_den_total_equals_num_total(p):
         s_part = s_part * (tv[x] + gamma) % p
     s_part = s_part * pow(tv[0] + gamma, usable - (1 << 16), p) % p
     assert s_part == num_s
+
+
+@pytest.mark.parametrize("usable", [1 << 16, (1 << 16) + 100])
+@pytest.mark.parametrize("p", [lk.P, lk.P_BN254])
+@pytest.mark.parametrize("minus", [1, 3])
+def test_properties_hold_for_equal_table_values(minus, p, usable):
+    """theta = -1 (T[2k] = T[2k + 1]: 32,768 pairs, T[0] among them) and theta = -3 (24,576 pairs,
+    T[0] = T[7], T[1] = T[2]) make table rows compress to equal values. The map of
+    permute_expression_pair pools them: one run of equal inputs, one run start, and the pooled
+    leftovers on the repeated rows. The defining properties hold as for distinct values."""
+    theta = p - minus
+    T = lk.table_values(theta, p)
+    assert len(set(T)) == {1: 32768, 3: 40960}[minus]
+    assert T[0] == T[1 if minus == 1 else 7]
+    a0, a1, a2 = _rows(usable, zero_frac=0.1)
+    _, beta, gamma = _chal(p)
+    A, S, Ap, Sp, z = lk.columns(a0, a1, a2, usable, theta, beta, gamma, p)
+    # the case is hit: table rows of equal value that both occur among the inputs
+    rows_of = {}
+    for x in set(int(v) for v in a1):
+        rows_of.setdefault(T[x], []).append(x)
+    assert sum(1 for v in rows_of.values() if len(v) > 1) > 1000
+    assert Ap == sorted(A)
+    assert sorted(Sp) == sorted(S)
+    assert Ap[0] == Sp[0]
+    for i in range(1, usable):
+        assert Ap[i] == Sp[i] or Ap[i] == Ap[i - 1], i
+    # one run start per distinct input value, not one per table row
+    assert sum(1 for i in range(usable) if i == 0 or Ap[i] != Ap[i - 1]) == len(rows_of)
+    assert len(z) == usable + 1 and z[0] == 1 and z[-1] == 1
+    rep = [i for i in range(1, usable) if Ap[i] == Ap[i - 1]]
+    vals = [Sp[i] for i in rep]
+    assert vals == sorted(vals, reverse=True)

@@ -8,8 +8,13 @@
 // is a table row, so the sort is a counting sort over the 2^16 table rows in the order of
 // their compressed values:
 //   table pass (once per theta): T[x] = theta^2 tag(x) + theta x + spread(x) for x < 2^16,
-//     sorted by canonical value (one radix sort by the top 64-bit limb, ties -- about 2^-33
-//     likely -- ordered by the lower limbs), giving the rank order x_of_rank[r];
+//     sorted by canonical value (one radix sort by the top 64-bit limb, equal top limbs --
+//     about 2^-33 likely for a uniform challenge -- ordered by the lower limbs), giving the rank
+//     order x_of_rank[r]. Table rows whose full 256-bit values are equal (a theta solving
+//     theta^2 dtag + theta dx + dspread = 0 for two rows, e.g. theta = -1, -3, -5) stay adjacent
+//     ranks and are marked as one group: halo2's BTreeMap holds one key for them, so the scan
+//     below pools the group's input count and table multiplicity on its first rank (the head)
+//     and gives the other members none -- one run, one run start, one pool of leftovers;
 //   count:   histogram of the dense cell (a_1) over the circuit's rows (LDS-privatised, four
 //            workgroups per circuit, a quarter of the bins each), with the row check (tag,
 //            dense, spread) in table (first failing row reported);
@@ -98,19 +103,31 @@ __global__ __launch_bounds__(256) void lk_table_kernel(Chal ch, Fe* __restrict__
 // by position -- and writes its table index at that rank into the output order; a thread not in
 // a run copies its index. The rank order is then the order of the full 256-bit values, as four
 // LSD passes over the limbs would give. For a uniform challenge runs are pairs at most (2^-33
-// likely), but a structured one (theta = 3: every value below 2^192, one run of 2^16; theta = -3:
-// a long run just below p, out of order) makes long runs, which cost O(L) per thread here, with
-// L threads at once, instead of one thread's insertion sort (round 6; O(L^2) on one thread).
+// likely), but a structured one makes long runs (theta = 3: every value below 2^192, one run of
+// 2^16; theta = -2^40: 65,281 values below 2^192 in descending order of x; theta = -3: every
+// value is below 2^32 or within 2^18 of p, two long runs, in which 24,576 pairs of rows have
+// EQUAL full values, e.g. T[1] = T[2] = p - 2 and T[0] = T[7] = 0), which cost O(L) per thread
+// here, with L threads at once, instead of one thread's insertion sort (round 6; O(L^2) on one
+// thread).
+// Fully equal values keep their order by position, so they end as adjacent ranks; the same loop
+// tells a thread whether an equal value sits before or after it. pgrp gets the rank order again
+// with that in two flag bits for the rank scan (rank_run): GRP_PREV = equal to the rank before
+// (a group's later member), GRP_NEXT = equal to the rank after. A group's head is the rank with
+// GRP_NEXT alone. The flags depend on theta only (this scratch is per theta; counts are per
+// circuit).
+constexpr uint32_t GRP_PREV = 1u << 16, GRP_NEXT = 1u << 17;
 __global__ __launch_bounds__(256) void lk_tie_fix_kernel(const uint64_t* __restrict__ key,
                                                          const uint64_t* __restrict__ top,
                                                          const uint32_t* __restrict__ pin,
-                                                         uint32_t* __restrict__ pout) {
+                                                         uint32_t* __restrict__ pout,
+                                                         uint32_t* __restrict__ pgrp) {
   const uint32_t r = blockIdx.x * 256 + threadIdx.x;
   const uint64_t k = top[r];
   const uint32_t x = pin[r];
   const bool tl = r > 0 && top[r - 1] == k, tr = r + 1 < (uint32_t)TROWS && top[r + 1] == k;
   if (!tl && !tr) {
     pout[r] = x;
+    pgrp[r] = x;
     return;
   }
   uint32_t lo = 0, hi = r;  // the run's first index: the first with top == k
@@ -129,14 +146,17 @@ __global__ __launch_bounds__(256) void lk_tie_fix_kernel(const uint64_t* __restr
   }
   const uint32_t e = lo;
   const uint64_t a2 = key[2ull * TROWS + x], a1 = key[(uint64_t)TROWS + x], a0 = key[x];
-  uint32_t rank = 0;
+  uint32_t rank = 0, grp = 0;
 #pragma unroll 8
   for (uint32_t q = s; q < e; q++) {  // (unrolled: eight members' loads in flight at once)
     const uint32_t y = pin[q];
     const uint64_t b2 = key[2ull * TROWS + y], b1 = key[(uint64_t)TROWS + y], b0 = key[y];
+    const bool same = b2 == a2 && b1 == a1 && b0 == a0;
     rank += (b2 != a2 ? b2 < a2 : b1 != a1 ? b1 < a1 : b0 != a0 ? b0 < a0 : q < r) ? 1u : 0u;
+    grp |= same ? (q < r ? GRP_PREV : q > r ? GRP_NEXT : 0u) : 0u;
   }
   pout[s + rank] = x;
+  pgrp[s + rank] = x | grp;
 }
 
 // ------------------------------------------------------------------ per-circuit passes
@@ -217,38 +237,65 @@ constexpr int SAMPLE = TROWS / SAMP;  // every SAMP-th pos / lstart entry, for l
 constexpr int SC_PARTS = 16, SC_THREADS = 256, SC_PER = TROWS / (SC_PARTS * SC_THREADS);
 static_assert(SC_PER == 16, "one search sample per thread");
 
-// the counts of this thread's SC_PER ranks (rank order read as 16-byte vectors), the index of the
-// rank holding table row 0 (-1: none), and the four sums: rows, runs, leftover table
-// multiplicity, ranks with leftovers
+// the counts and table multiplicities of this thread's SC_PER ranks (rank order read as 16-byte
+// vectors; table row 0's multiplicity is mult0), and the four sums: rows, runs, leftover table
+// multiplicity, ranks with leftovers.
+// Table rows of equal value (lk_tie_fix_kernel's flags in perm's bits 16 and 17) are one rank, as
+// halo2's map holds one key for them: the group's head carries the sum of its members' counts and
+// of their table multiplicities (row 0's mult0 among them), the other members carry count 0 and
+// multiplicity 0 -- an empty run with no leftover items, which pos / dcnt / the compacted leftover
+// ranks pass over as they pass over a rank no row uses. A head reads its members' counts itself,
+// wherever they lie (beyond this thread's ranks, in another part): a group may have any size, and
+// no thread needs another's sums. Without a flag among the thread's ranks (any theta that keeps
+// the table values distinct) none of this runs.
 struct RankRun {
-  uint32_t nv[SC_PER];
+  uint32_t nv[SC_PER];  // input rows of each rank (a group's: at its head)
+  uint32_t mv[SC_PER];  // its table multiplicity (likewise)
   uint32_t xv[SC_PER];  // the table index of each rank
-  int iz;
   uint32_t sc, sd, sl, sr;
 };
 __device__ __forceinline__ RankRun rank_run(const uint32_t* __restrict__ perm, const uint32_t* __restrict__ cnt,
                                             uint32_t r0, uint32_t mult0) {
   RankRun R;
-  R.iz = -1;
+  uint32_t fl[SC_PER], any = 0;
   const uint4* pv = reinterpret_cast<const uint4*>(perm + r0);
 #pragma unroll
   for (int i = 0; i < SC_PER / 4; i++) {
     const uint4 x = pv[i];
-    R.nv[4 * i] = cnt[x.x];
-    R.nv[4 * i + 1] = cnt[x.y];
-    R.nv[4 * i + 2] = cnt[x.z];
-    R.nv[4 * i + 3] = cnt[x.w];
-    R.xv[4 * i] = x.x;
-    R.xv[4 * i + 1] = x.y;
-    R.xv[4 * i + 2] = x.z;
-    R.xv[4 * i + 3] = x.w;
-    R.iz = x.x == 0 ? 4 * i : x.y == 0 ? 4 * i + 1 : x.z == 0 ? 4 * i + 2 : x.w == 0 ? 4 * i + 3 : R.iz;
+    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      R.xv[4 * i + j] = w[j] & 0xffffu;
+      fl[4 * i + j] = w[j] & (GRP_PREV | GRP_NEXT);
+      any |= w[j];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < SC_PER; i++) {
+    R.nv[i] = cnt[R.xv[i]];
+    R.mv[i] = R.xv[i] == 0 ? mult0 : 1u;
+  }
+  if (any & (GRP_PREV | GRP_NEXT)) {
+#pragma unroll
+    for (int i = 0; i < SC_PER; i++) {
+      if (fl[i] & GRP_PREV) {
+        R.nv[i] = 0;
+        R.mv[i] = 0;
+      } else if (fl[i] & GRP_NEXT) {
+        for (uint32_t q = r0 + i + 1; q < (uint32_t)TROWS; q++) {
+          const uint32_t y = perm[q];
+          if (!(y & GRP_PREV)) break;
+          R.nv[i] += cnt[y & 0xffffu];
+          R.mv[i] += (y & 0xffffu) == 0 ? mult0 : 1u;
+        }
+      }
+    }
   }
   R.sc = R.sd = R.sl = R.sr = 0;
 #pragma unroll
   for (int i = 0; i < SC_PER; i++) {
     const uint32_t n = R.nv[i];
-    const uint32_t m = (i == R.iz ? mult0 : 1u) - (n ? 1u : 0u);
+    const uint32_t m = R.mv[i] - (n ? 1u : 0u);
     R.sc += n;
     R.sd += n ? 1u : 0u;
     R.sl += m;
@@ -333,7 +380,7 @@ __global__ __launch_bounds__(SC_THREADS) void lk_scan_write(const uint32_t* __re
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const uint32_t n = R.nv[4 * i + j];
-      const uint32_t m = (4 * i + j == R.iz ? mult0 : 1u) - (n ? 1u : 0u);  // leftovers
+      const uint32_t m = R.mv[4 * i + j] - (n ? 1u : 0u);  // leftovers (0 - 0 for a group's later members)
       pq[j] = ec;
       ed += n ? 1u : 0u;
       dq[j] = ed;
@@ -1068,6 +1115,7 @@ struct Carve {
   uint64_t* kout;  // TROWS
   uint32_t* perm;   // TROWS: the sort's input (x), then the rank order (lk_tie_fix_kernel)
   uint32_t* perm2;  // TROWS: the sort's output (by top limb)
+  uint32_t* pgrp;   // TROWS: the rank order with the equal-value group flags (the rank scan's)
   uint32_t* count;  // group x TROWS
   uint32_t* pos;
   uint32_t* dcnt;
@@ -1111,6 +1159,7 @@ Carve carve(void* base, uint32_t group, uint64_t usable) {
   k.kout = (uint64_t*)take(8ull * TROWS);
   k.perm = (uint32_t*)take(4ull * TROWS);
   k.perm2 = (uint32_t*)take(4ull * TROWS);
+  k.pgrp = (uint32_t*)take(4ull * TROWS);
   k.count = (uint32_t*)take(4ull * TROWS * group);
   k.pos = (uint32_t*)take(4ull * TROWS * group);
   k.dcnt = (uint32_t*)take(4ull * TROWS * group);
@@ -1177,7 +1226,8 @@ hipError_t run_lookup(const uint32_t* d_advice, uint64_t total_rows, const uint6
     if (e != hipSuccess) return e;
   }
   // the tie fix reads the sort's order (perm2) and writes the final one over the sort's input
-  hipLaunchKernelGGL(lk_tie_fix_kernel, tb, dim3(256), 0, st, k.key, k.kout, k.perm2, k.perm);
+  // (for the z pass) and, flagged with the groups of equal values, into pgrp (for the rank scan)
+  hipLaunchKernelGGL(lk_tie_fix_kernel, tb, dim3(256), 0, st, k.key, k.kout, k.perm2, k.perm, k.pgrp);
   uint32_t* pa = k.perm;
   if ((e = hipEventRecord(ss.sorted, st)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(d_first_bad, 0xff, 8ull * n_circuits, s)) != hipSuccess) return e;
@@ -1204,8 +1254,8 @@ hipError_t run_lookup(const uint32_t* d_advice, uint64_t total_rows, const uint6
     hipLaunchKernelGGL(lk_count_kernel, dim3(CNT_SPLIT, g), dim3(CNT_THREADS), 0, s, d_advice,
                        total_rows, d_row_begin, c0, usable_rows, k.count, d_first_bad);
     if (c0 == 0 && B2F_LK_SORT_SIDE && (e = hipStreamWaitEvent(s, ss.sorted, 0)) != hipSuccess) return e;
-    hipLaunchKernelGGL(lk_scan_sums, dim3(SC_PARTS, g), dim3(SC_THREADS), 0, s, pa, k.count, usable_rows, k.part);
-    hipLaunchKernelGGL(lk_scan_write, dim3(SC_PARTS, g), dim3(SC_THREADS), 0, s, pa, k.count, usable_rows,
+    hipLaunchKernelGGL(lk_scan_sums, dim3(SC_PARTS, g), dim3(SC_THREADS), 0, s, k.pgrp, k.count, usable_rows, k.part);
+    hipLaunchKernelGGL(lk_scan_write, dim3(SC_PARTS, g), dim3(SC_THREADS), 0, s, k.pgrp, k.count, usable_rows,
                        k.part, k.pos, k.dcnt, k.lrank, k.lstart, k.samp, k.nlr);
     hipLaunchKernelGGL(lk_block_kernel, dim3((uint32_t)((nb + BK_T - 1) / BK_T), g), dim3(BK_T), 0, s, usable_rows,
                        nb, k.pos, k.dcnt, k.lstart, k.samp, k.nlr, k.blk);
