@@ -2,7 +2,9 @@
 
 TEST INFRASTRUCTURE ONLY: tests/ use this as the checker for b2f_permutation_mapping and
 b2f_permutation_columns_dev (VERDICT r1 item 9, the widening of SURVEY.md §8(f) row 2);
-nothing in the product path imports it. Pure-Python big integers: small circuits only.
+nothing in the product path imports it. Pure-Python big integers: `columns` for small circuits;
+`columns_fast` (the same values, pinned to `columns` in tests/test_permutation_oracle.py) for
+circuits of a few hundred thousand rows and domains up to 2^23.
 
 The algorithm lives in halo2_proofs 0.3.0 (crates.io, /root/reference/Cargo.lock:841-855),
 which is not in /root/reference; restated from its published source:
@@ -141,6 +143,131 @@ def columns(adv, offsets, k, usable, beta, gamma, chunk_len, p, copies_of):
         zs.append(z)
         last = z[usable]
     return sigma, zs
+
+
+class Factors:
+    """What columns_fast needs of the rows i < used, which do not depend on `usable`: per column
+    set the factor lists num / den (as `columns` forms them), and the z rows 0..used they give
+    (made once, on first use)."""
+
+    def __init__(self, p, k, used, beta, gamma, chunk_len, num, den):
+        self.p, self.k, self.used = p, k, used
+        self.beta, self.gamma, self.chunk_len = beta, gamma, chunk_len
+        self.num, self.den = num, den
+        self._head = None
+
+    def z_head(self):
+        if self._head is None:
+            p, last, head = self.p, 1, []
+            for num, den in zip(self.num, self.den):
+                inv = _batch_invert(den, p)
+                z = [last]
+                for i in range(self.used):
+                    z.append(z[-1] * inv[i] % p * num[i] % p)
+                head.append(z)
+                last = z[-1]
+            self._head = head
+        return self._head
+
+
+def factors(adv, offsets, k, beta, gamma, chunk_len, p, copies_of):
+    """The factors of `columns` over the rows i < used, with each instance's mapping built once
+    per `rounds` (the copies never leave their instance, so the circuit's Assembly is the
+    instances' side by side) and beta w^i formed once per row, not once per column."""
+    used = int(offsets[-1])
+    assert used < (1 << k)
+    omega, delta = domain(p, k)
+    dp = [pow(delta, j, p) for j in range(NCOL)]
+    bw = [beta % p] * max(used, 1)  # beta w^i
+    for i in range(1, used):
+        bw[i] = bw[i - 1] * omega % p
+    maps = {}
+    fn = [[0] * used for _ in range(NCOL)]  # per column: v + beta delta^j w^i + gamma
+    fd = [[0] * used for _ in range(NCOL)]  # per column: v + beta sigma_j(w^i) + gamma
+    for t in range(len(offsets) - 1):
+        s, e = int(offsets[t]), int(offsets[t + 1])
+        rounds = (e - s - 228) // 416
+        if rounds not in maps:
+            maps[rounds] = instance_mapping(rounds, copies_of(rounds))
+        m = maps[rounds]
+        for j in range(NCOL):
+            col, mj, dj, nj, dnj = adv[j + 1], m[j], dp[j], fn[j], fd[j]
+            for i in range(s, e):
+                vg = int(col[i]) + gamma
+                mm = mj[i - s]
+                nj[i] = (vg + dj * bw[i]) % p
+                dnj[i] = (vg + dp[mm >> 29] * bw[s + (mm & 0x1FFFFFFF)]) % p
+    num, den = [], []
+    for j0 in range(0, NCOL, chunk_len):
+        n, d = fn[j0], fd[j0]
+        for j in range(j0 + 1, min(j0 + chunk_len, NCOL)):
+            n = [a * b % p for a, b in zip(n, fn[j])]
+            d = [a * b % p for a, b in zip(d, fd[j])]
+        assert all(n) and all(d), "a factor of a row < used is zero"
+        num.append(n)
+        den.append(d)
+    return Factors(p, k, used, beta, gamma, chunk_len, num, den)
+
+
+def _tail_has_zero_factor(p, k, used, usable, beta, gamma):
+    """Whether beta delta^j w^i + gamma is zero for some column j and row used <= i < usable
+    (num_i = den_i there: cells zero, identity mapping). Zero means w^i = -gamma / (beta
+    delta^j) =: t, which needs t in the 2^k-th roots of unity: only then are the rows walked."""
+    omega, delta = domain(p, k)
+    beta, gamma = beta % p, gamma % p
+    if usable <= used:
+        return False
+    if beta == 0:
+        return gamma == 0
+    for j in range(NCOL):
+        t = (p - gamma) * pow(beta * pow(delta, j, p), p - 2, p) % p
+        if pow(t, 1 << k, p) != 1:
+            continue
+        w = pow(omega, used, p)
+        for _ in range(used, usable):
+            if w == t:
+                return True
+            w = w * omega % p
+    return False
+
+
+def columns_fast(adv, offsets, k, usable, beta, gamma, chunk_len, p, copies_of, sigma=True,
+                 fac=None):
+    """`columns` for large circuits: the same arguments and results (sigma None when not asked
+    for). Derived from `columns`, not a second algorithm: the rows i < used come from `factors`
+    (pass `fac` to share them between several `usable`); on the rows i >= used the cells are
+    zero and the mapping the identity, so num_i = den_i and, no factor being zero (asserted),
+    every z row used..usable equals z[used]; sigma there is delta^j w^i."""
+    n_rows = 1 << k
+    used = int(offsets[-1])
+    assert used <= usable < n_rows
+    if fac is None:
+        fac = factors(adv, offsets, k, beta, gamma, chunk_len, p, copies_of)
+    assert (fac.p, fac.k, fac.used, fac.beta, fac.gamma, fac.chunk_len) == \
+        (p, k, used, beta, gamma, chunk_len)
+    assert not _tail_has_zero_factor(p, k, used, usable, beta, gamma), \
+        "a factor of a row >= used is zero"
+    zs = [z + [z[-1]] * (usable - used) for z in fac.z_head()]
+    sig = None
+    if sigma:
+        omega, delta = domain(p, k)
+        dp = [pow(delta, j, p) for j in range(NCOL)]
+        wp = [1] * n_rows
+        for i in range(1, n_rows):
+            wp[i] = wp[i - 1] * omega % p
+        sig = [[dj * w % p for w in wp] for dj in dp]  # the identity; the instances' rows follow
+        maps = {}
+        for t in range(len(offsets) - 1):
+            s, e = int(offsets[t]), int(offsets[t + 1])
+            rounds = (e - s - 228) // 416
+            if rounds not in maps:
+                maps[rounds] = instance_mapping(rounds, copies_of(rounds))
+            for j in range(NCOL):
+                mj, sj = maps[rounds][j], sig[j]
+                for i in range(s, e):
+                    mm = mj[i - s]
+                    sj[i] = dp[mm >> 29] * wp[s + (mm & 0x1FFFFFFF)] % p
+    return sig, zs
 
 
 def _batch_invert(vals, p):

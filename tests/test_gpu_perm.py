@@ -2,7 +2,10 @@
 r1 item 9) with the CPU restatement of halo2_proofs 0.3.0's keygen + prover
 (oracle/permutation.py): sigma and every z bit-exact in all four field forms and several
 column-set sizes, for circuits made of all or part of a batch; z closes to 1 on the valid
-trace and not on a broken copy. Needs an MI355X (`-m gpu`)."""
+trace and not on a broken copy. Everything here is one 4,096-row block of the grand product
+(k = 12); tests/test_gpu_perm_shapes.py compares the sizes at which its passes change shape
+(several blocks, the two block scans, runs of blocks per scan thread, the large coset tables).
+Needs an MI355X (`-m gpu`)."""
 import numpy as np
 import pytest
 

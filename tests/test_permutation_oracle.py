@@ -80,6 +80,66 @@ def test_host_field_constants_match_restatement():
             assert (field.omega(f, k), field.delta(f)) == pm.domain(p, k)
 
 
+@pytest.fixture(scope="module")
+def fast_trace(orc):
+    x = random_inputs(9, (0, 1, 2, 5), 83)
+    adv, fixed, h_out, off = orc.fill(_orc_inputs(x, orc))
+    return adv, off.astype(np.int64)
+
+
+# (k, instances [i0, i1)): the k = 12 circuits do not start at trace row 0
+FAST_CIRCUITS = {12: (2, 5), 13: (0, 6)}
+
+
+@pytest.mark.parametrize("chunk", [1, 3, 8])
+@pytest.mark.parametrize("p", [pm.P_PALLAS, pm.P_BN254], ids=["pallas", "bn254"])
+@pytest.mark.parametrize("k", [12, 13])
+def test_columns_fast_equals_columns(orc, fast_trace, k, p, chunk):
+    """columns_fast (per-instance mappings, the constant tail) against columns, sigma and every
+    z row: used < usable at both sizes, used == usable at k = 12."""
+    adv, off = fast_trace
+    i0, i1 = FAST_CIRCUITS[k]
+    s, e = int(off[i0]), int(off[i1])
+    assert (s > 0) == (k == 12)
+    cadv, rel = adv[:, s:e], off[i0:i1 + 1] - s
+    used = e - s
+    rng = np.random.default_rng(84 + k + chunk)
+    beta = int.from_bytes(rng.bytes(32), "little") % p
+    gamma = int.from_bytes(rng.bytes(32), "little") % p
+    fac = pm.factors(cadv, rel, k, beta, gamma, chunk, p, orc.copies)
+    for usable in ((1 << k) - 7, used) if k == 12 else ((1 << k) - 7,):
+        assert used <= usable
+        sigma, zs = pm.columns(cadv, rel, k, usable, beta, gamma, chunk, p, orc.copies)
+        fsigma, fzs = pm.columns_fast(cadv, rel, k, usable, beta, gamma, chunk, p, orc.copies,
+                                      fac=fac)
+        assert fsigma == sigma
+        assert len(fzs) == len(zs) == -(-8 // chunk)
+        for c in range(len(zs)):
+            assert len(fzs[c]) == usable + 1
+            assert fzs[c] == zs[c], "z set %d" % c
+        assert zs[-1][usable] == 1
+    # without shared factors, and without sigma
+    none, fz2 = pm.columns_fast(cadv, rel, k, used, beta, gamma, chunk, p, orc.copies, sigma=False)
+    assert none is None and fz2 == [z[:used + 1] for z in fzs]
+
+
+def test_columns_fast_refuses_a_zero_tail_factor(orc, fast_trace):
+    """gamma = -beta delta^2 w^i for a row i past the instances makes num_i = den_i = 0 there:
+    the rows after it are not z[used] (columns' batch inversion leaves zeros), so columns_fast
+    asserts rather than return the constant."""
+    adv, off = fast_trace
+    p, k = pm.P_PALLAS, 12
+    rel = off[:3] - off[0]
+    used = int(rel[-1])
+    w, d = pm.domain(p, k)
+    beta = 12345
+    gamma = (p - beta * d * d % p * pow(w, used + 40, p)) % p
+    fac = pm.factors(adv, rel, k, beta, gamma, 3, p, orc.copies)
+    pm.columns_fast(adv, rel, k, used + 40, beta, gamma, 3, p, orc.copies, sigma=False, fac=fac)
+    with pytest.raises(AssertionError):
+        pm.columns_fast(adv, rel, k, used + 41, beta, gamma, 3, p, orc.copies, sigma=False, fac=fac)
+
+
 @pytest.mark.parametrize("p,chunk", [(pm.P_PALLAS, 3), (pm.P_BN254, 8), (pm.P_PALLAS, 1)])
 def test_z_closes_on_valid_trace_and_not_on_broken_copy(orc, p, chunk):
     x = random_inputs(3, (0, 1, 2), 81)

@@ -235,7 +235,10 @@ __global__ __launch_bounds__(gp::BLK) __attribute__((amdgpu_waves_per_eu(PmWaves
     // the wave's first row -> its instance (one search per wave), then this lane's first row
     const uint64_t wq = __builtin_amdgcn_readfirstlane((uint32_t)(blockIdx.x * gp::BLK + (t & ~63u)));
     const uint64_t rb = q * gp::ZC, re = rb + gp::ZC < usable ? rb + gp::ZC : usable;
-    uint32_t ii = inst_of_wave(I, wq * gp::ZC < usable ? wq * gp::ZC : 0, rb < usable ? rb : 0);
+    // a lane without a chunk (rb >= usable) fetches the wave's first row: a row before it would
+    // be read through the context of the wave's instance, below that instance's pattern
+    const uint64_t wb = wq * gp::ZC < usable ? wq * gp::ZC : 0, rf = rb < usable ? rb : wb;
+    uint32_t ii = inst_of_wave(I, wb, rf);
     // the lane's instance context, refreshed when its rows cross an instance start (an instance
     // has >= 228 rows, so at most once per chunk)
     uint64_t s_lo = ~0ull, s_hi = ~0ull, pat = 0;
@@ -270,7 +273,7 @@ __global__ __launch_bounds__(gp::BLK) __attribute__((amdgpu_waves_per_eu(PmWaves
       }                                                                                          \
     } while (0)
     RowIn cur;
-    PM_FETCH(cur, rb < usable ? rb : 0);
+    PM_FETCH(cur, rf);
     uint64_t cur_lo = s_lo;
 #pragma unroll 1
     for (uint64_t r = rb; r < re; r++) {
