@@ -312,6 +312,35 @@ B2F_API int b2f_permutation_columns_dev(b2f_ctx* ctx, const uint32_t* d_advice, 
                                         uint64_t* d_sigma, uint64_t* d_z, uint64_t out_rows,
                                         void* stream);
 
+/* The permutation z columns of n_circuits circuits in one call (halo2's create_proof takes a
+ * slice of circuits and draws one beta, gamma for all of them; the shape of
+ * b2f_lookup_columns_dev). h_offsets[0..n] is the host row map of the instances in d_advice, as
+ * for b2f_permutation_columns_dev; h_circuit_first[0..n_circuits] holds strictly increasing
+ * instance indices, h_circuit_first[n_circuits] <= n: circuit c is made of the instances
+ * [h_circuit_first[c], h_circuit_first[c + 1]) and its row 0 is trace row
+ * h_offsets[h_circuit_first[c]] (instances before the first and after the last boundary belong to
+ * no circuit). k, usable_rows, omega, delta, beta, gamma, chunk_len and form are shared. With
+ * sets = ceil(8 / chunk_len), column set s of circuit c goes to
+ *   d_z[((c * sets + s) * out_rows + i) * 4 + limb],  rows 0 ..= usable_rows,
+ * bit for bit what b2f_permutation_columns_dev writes for that circuit alone with d_sigma = NULL:
+ * every circuit's first set starts at 1, its sets chain, cells past its instances are zero and
+ * map to themselves. There is no sigma argument: sigma is keygen data, computed once per circuit
+ * shape by b2f_permutation_sigma_dev. The circuits run in groups of
+ * clamp(2^24 / usable_rows, 1, n_circuits) (and at most 65,535 / sets), so the scratch is that
+ * many times the single call's per-circuit scratch whatever n_circuits is; the coset tables are
+ * built once per call and one instance table goes up for all circuits (same host setup and
+ * waits as the single call). B2F_ERR_ROWS names the first circuit that uses more than
+ * usable_rows rows. A zero denominator product in any circuit reports B2F_ERR_FIELD at b2f_sync;
+ * the other circuits' columns are written all the same. One call is one B2F_KERNEL_PERM region.
+ * Asynchronous on `stream`. */
+B2F_API int b2f_permutation_columns_batch_dev(b2f_ctx* ctx, const uint32_t* d_advice, uint64_t total_rows,
+                                              const uint64_t* h_offsets, size_t n,
+                                              const uint64_t* h_circuit_first, uint32_t n_circuits,
+                                              uint32_t k, uint64_t usable_rows, const uint64_t omega[4],
+                                              const uint64_t delta[4], const uint64_t beta[4],
+                                              const uint64_t gamma[4], uint32_t chunk_len, uint32_t form,
+                                              uint64_t* d_z, uint64_t out_rows, void* stream);
+
 /* Keygen's permutation polynomials alone (halo2_proofs 0.3.0 plonk/permutation/keygen.rs
  * build_pk: the sigma columns depend on the circuit's structure, not on a witness): the same
  * d_sigma that b2f_permutation_columns_dev writes for the row map h_offsets[0..n], domain 2^k,

@@ -108,6 +108,9 @@ SIGNATURES = [
     ("b2f_permutation_mapping", U64, [ctypes.c_uint32, P, U64]),
     ("b2f_permutation_columns_dev", I32, [P, P, U64, P, SIZE, ctypes.c_uint32, U64, P, P, P, P,
                                           ctypes.c_uint32, ctypes.c_uint32, P, P, U64, P]),
+    ("b2f_permutation_columns_batch_dev", I32, [P, P, U64, P, SIZE, P, ctypes.c_uint32,
+                                                ctypes.c_uint32, U64, P, P, P, P, ctypes.c_uint32,
+                                                ctypes.c_uint32, P, U64, P]),
     ("b2f_permutation_sigma_dev", I32, [P, P, SIZE, ctypes.c_uint32, P, P, ctypes.c_uint32, P, U64, P]),
     ("b2f_sync", I32, [P, P]),
     ("b2f_fill", I32, [P, P, SIZE, P, P, P]),

@@ -180,6 +180,21 @@ class Engine:
             int(usable_rows), lim[0], lim[1], lim[2], lim[3], int(chunk_len), int(form),
             _vp(d_sigma) if d_sigma else None, _vp(d_z), int(out_rows), _vp(stream)))
 
+    def permutation_columns_batch_dev(self, d_adv, total_rows, h_offsets, h_circuit_first, k,
+                                      usable_rows, omega, delta, beta, gamma, chunk_len, form, d_z,
+                                      out_rows, stream=0):
+        """b2f_permutation_columns_batch_dev; h_offsets: host u64 row map of the instances,
+        h_circuit_first: the circuits' instance boundaries (n_circuits + 1 of them),
+        omega/delta/beta/gamma Python ints (canonical)."""
+        off = np.ascontiguousarray(h_offsets, dtype=np.uint64)
+        first = np.ascontiguousarray(h_circuit_first, dtype=np.uint64)
+        lim = [(ctypes.c_uint64 * 4)(*[(int(v) >> (64 * i)) & (2**64 - 1) for i in range(4)])
+               for v in (omega, delta, beta, gamma)]
+        self._check(self.lib.b2f_permutation_columns_batch_dev(
+            self.ctx, _vp(d_adv), int(total_rows), _np_ptr(off), len(off) - 1, _np_ptr(first),
+            max(len(first) - 1, 0), int(k), int(usable_rows), lim[0], lim[1], lim[2], lim[3],
+            int(chunk_len), int(form), _vp(d_z), int(out_rows), _vp(stream)))
+
     def permutation_sigma_dev(self, h_offsets, k, omega, delta, form, d_sigma, out_rows, stream=0):
         """b2f_permutation_sigma_dev (keygen: the sigma columns alone); omega/delta Python ints."""
         off = np.ascontiguousarray(h_offsets, dtype=np.uint64)
@@ -338,6 +353,29 @@ class DeviceBatch:
                                     chunk_len, form, sig.data_ptr() if sigma else 0,
                                     z.data_ptr(), n_rows, s)
         return sig, z
+
+    def permutation_columns_batch(self, eng, k, usable_rows, beta, gamma, circuits, chunk_len=3,
+                                  form=_lib.FP_MONTGOMERY, stream=None):
+        """The permutation z columns of C circuits in one call, every circuit in its own 2^k-row
+        domain under the same challenges: `circuits` = the instance boundaries [i_0, i_1, ...,
+        i_C], circuit c holding instances [i_c, i_{c+1}). Returns z int64 [C, sets, 2^k, 4] with
+        rows 0..usable_rows written, z[c] equal to permutation_columns(instances=(i_c, i_{c+1}),
+        sigma=False)[1] -- see b2f_permutation_columns_batch_dev."""
+        from . import field
+
+        torch = self.torch
+        first = [int(i) for i in circuits]
+        f = field.of_form(form)
+        n_rows = 1 << int(k)
+        sets = (8 + chunk_len - 1) // chunk_len
+        z = torch.empty((max(len(first) - 1, 0), sets, n_rows, 4), dtype=torch.int64,
+                        device=self.advice.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        eng.permutation_columns_batch_dev(self.advice.data_ptr(), self.total_rows, self.offsets_host,
+                                          first, k, usable_rows, field.omega(f, int(k)),
+                                          field.delta(f), beta, gamma, chunk_len, form, z.data_ptr(),
+                                          n_rows, s)
+        return z
 
     def permutation_sigma(self, eng, k, form=_lib.FP_MONTGOMERY, instances=None, stream=None):
         """Keygen's sigma columns (int64 [8, 2^k, 4]) of the circuit holding instances

@@ -274,11 +274,13 @@ __global__ __launch_bounds__(64) void gp_inv(Fe* __restrict__ dt, int* __restric
 #endif
 }
 
-// closing[c] = seed N / D (the value z[usable] ends at), for a chained next product
+// closing[c] = seed N / D (the value z[usable] ends at), for a chained next product; a lane
+// per product, any g (blocks of CLOSE_T)
+constexpr int CLOSE_T = 256;
 template <class F>
-__global__ void gp_close(const Fe* __restrict__ sn, const Fe* __restrict__ dinv, Fe* __restrict__ closing,
-                         uint32_t g) {
-  const uint32_t c = threadIdx.x;
+__global__ __launch_bounds__(CLOSE_T) void gp_close(const Fe* __restrict__ sn, const Fe* __restrict__ dinv,
+                                                    Fe* __restrict__ closing, uint32_t g) {
+  const uint32_t c = blockIdx.x * CLOSE_T + threadIdx.x;
   if (c < g) closing[c] = field::mul<F>(sn[c], dinv[c]);
 }
 
@@ -367,12 +369,17 @@ __global__ __launch_bounds__(256) void gp_write(uint64_t usable, bool mont, uint
 
 // Chained products: S[0] = 1, S[c] = S[c - 1] T[c - 1] with T[c] product c's closing value
 // for seed 1 (the permutation argument's column sets: each set's z starts where the previous
-// one closed).
+// one closed). The g products are g / len chains of `len` (one per circuit of a batch: every
+// chain restarts at 1), a lane per chain.
+constexpr int CHAIN_T = 64;
 template <class F>
-__global__ void gp_chain_seeds(const Fe* __restrict__ T, Fe* __restrict__ S, uint32_t g) {
-  if (threadIdx.x != 0) return;
+__global__ __launch_bounds__(CHAIN_T) void gp_chain_seeds(const Fe* __restrict__ T, Fe* __restrict__ S,
+                                                         uint32_t g, uint32_t len) {
+  const uint64_t c0 = ((uint64_t)blockIdx.x * CHAIN_T + threadIdx.x) * len;
+  if (c0 >= g) return;
+  const uint32_t c1 = c0 + len < g ? (uint32_t)(c0 + len) : g;
   Fe acc = field::one<F>();
-  for (uint32_t c = 0; c < g; c++) {
+  for (uint32_t c = (uint32_t)c0; c < c1; c++) {
     S[c] = acc;
     acc = field::mul<F>(acc, T[c]);
   }
@@ -432,11 +439,12 @@ hipError_t run_begin(uint32_t g, uint64_t usable, Fe* num, const Fe* den, Fe* zs
 // Second half: the block scan, the join with the inversion, closing values / chained seeds, and
 // z. With `chain` (2 g elements of scratch) the products are chained -- product c starts from
 // product c - 1's closing value, product 0 from 1 -- and still scanned side by side: their single
-// inversions run in parallel, the seeds are applied in gp_write.
+// inversions run in parallel, the seeds are applied in gp_write. chain_len: the products are
+// g / chain_len chains of that many products, each starting from 1 (0: one chain of all g).
 template <class F>
 hipError_t run_end(uint32_t g, uint64_t usable, bool mont, uint64_t* z_base, uint64_t z_stride,
                    Fe* num, const Fe* den, Fe* zs, const Fe* seed, Fe* closing, hipStream_t s,
-                   Fe* chain, Side side) {
+                   Fe* chain, Side side, uint32_t chain_len = 0) {
   Fe* post = nullptr;
   if (chain) {
     seed = nullptr;
@@ -451,8 +459,15 @@ hipError_t run_end(uint32_t g, uint64_t usable, bool mont, uint64_t* z_base, uin
   else
     hipLaunchKernelGGL(gp_scan<F>, dim3(g), dim3(SCAN_THREADS), 0, s, nb, k.tn, k.td, seed, k.sn);
   if (side.s2 && (e = hipStreamWaitEvent(s, side.join, 0)) != hipSuccess) return e;
-  if (closing) hipLaunchKernelGGL(gp_close<F>, dim3(1), dim3(256), 0, s, k.sn, k.dt, closing, g);
-  if (chain) hipLaunchKernelGGL(gp_chain_seeds<F>, dim3(1), dim3(64), 0, s, chain, post, g);
+  if (closing)
+    hipLaunchKernelGGL(gp_close<F>, dim3((g + CLOSE_T - 1) / CLOSE_T), dim3(CLOSE_T), 0, s, k.sn, k.dt,
+                       closing, g);
+  if (chain) {
+    if (chain_len == 0 || chain_len > g) chain_len = g;
+    const uint32_t chains = (g + chain_len - 1) / chain_len;
+    hipLaunchKernelGGL(gp_chain_seeds<F>, dim3((chains + CHAIN_T - 1) / CHAIN_T), dim3(CHAIN_T), 0, s, chain,
+                       post, g, chain_len);
+  }
   hipLaunchKernelGGL(gp_write<F>, dim3((uint32_t)((nq + 255) / 256), g), dim3(256), 0, s, usable, mont,
                      z_base, z_stride, num, den, k.zn, k.zd, k.tn, seed, post, k.dt);
   return hipGetLastError();

@@ -45,6 +45,9 @@ hipError_t launch_spread_table(uint64_t usable_rows, uint32_t form, uint64_t* d_
                                uint64_t out_rows, hipStream_t s);
 size_t perm_scratch_bytes(uint32_t k, uint64_t usable_rows, size_t n_inst, uint32_t chunk_len);
 size_t perm_sigma_scratch_bytes(uint32_t k);
+size_t perm_batch_scratch_bytes(uint32_t k, uint64_t usable_rows, uint32_t group, uint32_t chunk_len);
+uint32_t perm_batch_group(uint64_t usable_rows, uint32_t n_circuits, uint32_t chunk_len);
+uint32_t perm_circ_words();
 hipError_t launch_permutation_sigma(const uint64_t* d_inst, size_t n_inst, const uint32_t* d_pool, uint32_t k,
                                     const uint64_t* omega, const uint64_t* delta, uint32_t form,
                                     uint64_t* d_sigma, uint64_t out_rows, void* scratch, hipStream_t s);
@@ -55,6 +58,13 @@ hipError_t launch_permutation(const uint32_t* d_advice, uint64_t total_rows, uin
                               uint32_t chunk_len, uint32_t form, uint64_t* d_sigma, uint64_t* d_z,
                               uint64_t out_rows, void* scratch, int* sticky, hipStream_t s2,
                               hipEvent_t ev_fork, hipEvent_t ev_join, hipStream_t s);
+hipError_t launch_permutation_batch(const uint32_t* d_advice, uint64_t total_rows, const uint64_t* d_tab,
+                                    uint32_t n_circuits, uint32_t group, const uint32_t* d_pool,
+                                    uint32_t k, uint64_t usable_rows, const uint64_t* omega,
+                                    const uint64_t* delta, const uint64_t* beta, const uint64_t* gamma,
+                                    uint32_t chunk_len, uint32_t form, uint64_t* d_z, uint64_t out_rows,
+                                    void* scratch, int* sticky, hipStream_t s2, hipEvent_t ev_fork,
+                                    hipEvent_t ev_join, hipStream_t s);
 hipError_t launch_export_fp(const uint32_t* d_advice, uint64_t total_rows, uint64_t row_begin,
                             uint64_t nrows, uint32_t form, uint64_t* d_out, uint64_t out_rows,
                             int cu_count, unsigned* tctr, hipStream_t s);  // b2f_export.hip
@@ -1669,9 +1679,11 @@ namespace {
 // patterns (built once per rounds, pooled on the device), the instance table (pinned staging,
 // async upload) and the scratch (need_scr bytes). *row0 / *used: the circuit's first trace row
 // and its rows. Whatever the caller launches next is stream-ordered after the table upload.
-int perm_setup(b2f_ctx* ctx, const char* what, const uint64_t* h_offsets, size_t n, uint32_t k,
-               uint32_t form, const uint64_t* const* elems, int n_elems, size_t need_scr,
-               hipStream_t s, uint64_t* row0, uint64_t* used) {
+// Its steps, shared with the batch call (which stages a table of several circuits):
+// perm_check_fields, perm_rounds, perm_patterns, perm_stage (-> the pinned staging to fill),
+// perm_upload.
+int perm_check_fields(b2f_ctx* ctx, const char* what, uint32_t k, uint32_t form,
+                      const uint64_t* const* elems, int n_elems) {
   if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "%s: unknown form %u", what, form);
   if (k < 10 || k > 30) return set_err(ctx, B2F_ERR_ARG, "%s: k %u not in [10, 30]", what, k);
   static const uint64_t moduli[2][4] = {
@@ -1685,8 +1697,11 @@ int perm_setup(b2f_ctx* ctx, const char* what, const uint64_t* h_offsets, size_t
   };
   for (int i = 0; i < n_elems; i++)
     if (!canon(elems[i])) return set_err(ctx, B2F_ERR_ARG, "%s: omega/delta/beta/gamma not canonical field elements", what);
-  *row0 = h_offsets[0];
-  std::vector<uint32_t> need;
+  return B2F_OK;
+}
+// need: the rounds of instances 0 .. n - 1 of the row map (B2F_ERR_LAYOUT for a pair that is none)
+int perm_rounds(b2f_ctx* ctx, const char* what, const uint64_t* h_offsets, size_t n,
+                std::vector<uint32_t>& need) {
   for (size_t i = 0; i < n; i++) {
     const uint64_t R = h_offsets[i + 1] - h_offsets[i];
     if (h_offsets[i + 1] < h_offsets[i] || R < FIXED_ROWS || (R - FIXED_ROWS) % ROUND_ROWS ||
@@ -1694,9 +1709,13 @@ int perm_setup(b2f_ctx* ctx, const char* what, const uint64_t* h_offsets, size_t
       return set_err(ctx, B2F_ERR_LAYOUT, "%s: offsets[%zu..%zu] is not an instance", what, i, i + 1);
     need.push_back((uint32_t)((R - FIXED_ROWS) / ROUND_ROWS));
   }
-  *used = h_offsets[n] - *row0;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  // mapping patterns: build the missing ones, rebuild the device pool if it lacks any
+  return B2F_OK;
+}
+// mapping patterns of the rounds in need[i0, i1): build the missing ones, rebuild the device
+// pool if it lacks any
+int perm_patterns(b2f_ctx* ctx, const char* what, const std::vector<uint32_t>& all, size_t i0, size_t i1,
+                  hipStream_t s) {
+  const std::vector<uint32_t> need(all.begin() + i0, all.begin() + i1);
   bool rebuild = false;
   for (uint32_t r : need) {
     if (!ctx->pm_pat.count(r)) {
@@ -1719,10 +1738,12 @@ int perm_setup(b2f_ctx* ctx, const char* what, const uint64_t* h_offsets, size_t
     HIPCHK(ctx, hipMalloc(&ctx->d_pm_pool, 4 * pool.size()));
     HIPCHK(ctx, hipMemcpy(ctx->d_pm_pool, pool.data(), 4 * pool.size(), hipMemcpyHostToDevice));
   }
-  // instance table: n + 1 circuit start rows, then n pool offsets, staged in pinned host
-  // memory and uploaded asynchronously; the host waits only for the previous call's upload
-  // (so the staging can be rewritten), or for the whole stream when a device buffer grows
-  const size_t m = 2 * n + 1;
+  return B2F_OK;
+}
+// The instance table (m u64) is staged in pinned host memory and uploaded asynchronously; the
+// host waits only for the previous call's upload (so the staging can be rewritten), or for the
+// whole stream when a device buffer grows. *it: the staging to fill before perm_upload.
+int perm_stage(b2f_ctx* ctx, size_t m, uint64_t** it) {
   if (ctx->pm_inst_ev_live) {
     HIPCHK(ctx, hipEventSynchronize(ctx->pm_inst_ev));
     ctx->pm_inst_ev_live = false;
@@ -1735,9 +1756,10 @@ int perm_setup(b2f_ctx* ctx, const char* what, const uint64_t* h_offsets, size_t
     ctx->h_pm_inst_cap = m;
   }
   if (!ctx->pm_inst_ev) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->pm_inst_ev, hipEventDisableTiming));
-  uint64_t* it = ctx->h_pm_inst;
-  for (size_t i = 0; i <= n; i++) it[i] = h_offsets[i] - *row0;
-  for (size_t i = 0; i < n; i++) it[n + 1 + i] = ctx->pm_pool_off[need[i]];
+  *it = ctx->h_pm_inst;
+  return B2F_OK;
+}
+int perm_upload(b2f_ctx* ctx, size_t m, size_t need_scr, hipStream_t s) {
   if (m > ctx->pm_inst_cap || need_scr > ctx->pm_cap) {
     HIPCHK(ctx, hipStreamSynchronize(s));
     if (m > ctx->pm_inst_cap) {
@@ -1756,10 +1778,28 @@ int perm_setup(b2f_ctx* ctx, const char* what, const uint64_t* h_offsets, size_t
     }
   }
   // stream-ordered after the previous call's kernels, which read the same device table
-  HIPCHK(ctx, hipMemcpyAsync(ctx->d_pm_inst, it, 8 * m, hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d_pm_inst, ctx->h_pm_inst, 8 * m, hipMemcpyHostToDevice, s));
   HIPCHK(ctx, hipEventRecord(ctx->pm_inst_ev, s));
   ctx->pm_inst_ev_live = true;
   return B2F_OK;
+}
+int perm_setup(b2f_ctx* ctx, const char* what, const uint64_t* h_offsets, size_t n, uint32_t k,
+               uint32_t form, const uint64_t* const* elems, int n_elems, size_t need_scr,
+               hipStream_t s, uint64_t* row0, uint64_t* used) {
+  if (int rc = perm_check_fields(ctx, what, k, form, elems, n_elems)) return rc;
+  *row0 = h_offsets[0];
+  std::vector<uint32_t> need;
+  if (int rc = perm_rounds(ctx, what, h_offsets, n, need)) return rc;
+  *used = h_offsets[n] - *row0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = perm_patterns(ctx, what, need, 0, n, s)) return rc;
+  // n + 1 circuit start rows, then n pool offsets
+  const size_t m = 2 * n + 1;
+  uint64_t* it = nullptr;
+  if (int rc = perm_stage(ctx, m, &it)) return rc;
+  for (size_t i = 0; i <= n; i++) it[i] = h_offsets[i] - *row0;
+  for (size_t i = 0; i < n; i++) it[n + 1 + i] = ctx->pm_pool_off[need[i]];
+  return perm_upload(ctx, m, need_scr, s);
 }
 }  // namespace
 
@@ -1799,6 +1839,77 @@ B2F_API int b2f_permutation_columns_dev(b2f_ctx* ctx, const uint32_t* d_advice, 
                                  usable_rows, omega, delta, beta, gamma, chunk_len, form, d_sigma,
                                  d_z, out_rows, ctx->d_pm, ctx->d_status + 2, ctx->s2, ctx->ev_fork,
                                  ctx->ev_join, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API int b2f_permutation_columns_batch_dev(b2f_ctx* ctx, const uint32_t* d_advice, uint64_t total_rows,
+                                              const uint64_t* h_offsets, size_t n,
+                                              const uint64_t* h_circuit_first, uint32_t n_circuits,
+                                              uint32_t k, uint64_t usable_rows, const uint64_t omega[4],
+                                              const uint64_t delta[4], const uint64_t beta[4],
+                                              const uint64_t gamma[4], uint32_t chunk_len, uint32_t form,
+                                              uint64_t* d_z, uint64_t out_rows, void* stream) {
+  const char* what = "permutation batch";
+  if (!ctx) return B2F_ERR_ARG;
+  if (!d_advice || !h_offsets || !h_circuit_first || !omega || !delta || !beta || !gamma || !d_z || n == 0)
+    return set_err(ctx, B2F_ERR_ARG, "%s: null buffer or no instances", what);
+  if (n_circuits == 0) return set_err(ctx, B2F_ERR_ARG, "%s: no circuits", what);
+  if (n > 0xffffffffull) return set_err(ctx, B2F_ERR_ARG, "%s: more than 2^32 instances", what);
+  for (uint32_t c = 0; c < n_circuits; c++)
+    if (h_circuit_first[c + 1] <= h_circuit_first[c] || h_circuit_first[c + 1] > n)
+      return set_err(ctx, B2F_ERR_ARG, "%s: circuit %u: instances [%llu, %llu) of %zu (boundaries must "
+                     "increase strictly and end at or before n)", what, c,
+                     (unsigned long long)h_circuit_first[c], (unsigned long long)h_circuit_first[c + 1], n);
+  if (chunk_len < 1 || chunk_len > PM_COLS)
+    return set_err(ctx, B2F_ERR_ARG, "%s: chunk_len %u not in [1, 8]", what, chunk_len);
+  if ((uintptr_t)d_z & 15) return set_err(ctx, B2F_ERR_ARG, "%s: d_z must be 16-byte aligned", what);
+  const uint64_t* elems[4] = {omega, delta, beta, gamma};
+  if (int rc = perm_check_fields(ctx, what, k, form, elems, 4)) return rc;
+  const uint64_t n_rows = 1ull << k;
+  if (usable_rows >= n_rows)
+    return set_err(ctx, B2F_ERR_ROWS, "%s: need usable_rows %llu < 2^k", what, (unsigned long long)usable_rows);
+  if (out_rows < usable_rows + 1) return set_err(ctx, B2F_ERR_ROWS, "%s: out_rows < usable_rows + 1", what);
+  std::vector<uint32_t> need;
+  if (int rc = perm_rounds(ctx, what, h_offsets, n, need)) return rc;
+  if (h_offsets[n] > total_rows) return set_err(ctx, B2F_ERR_ROWS, "%s: instances past total_rows", what);
+  for (uint32_t c = 0; c < n_circuits; c++) {
+    const uint64_t used = h_offsets[h_circuit_first[c + 1]] - h_offsets[h_circuit_first[c]];
+    if (used > usable_rows)
+      return set_err(ctx, B2F_ERR_ROWS, "%s: circuit %u uses %llu rows > usable_rows %llu", what, c,
+                     (unsigned long long)used, (unsigned long long)usable_rows);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t i0 = h_circuit_first[0], i1 = h_circuit_first[n_circuits];
+  if (int rc = perm_patterns(ctx, what, need, i0, i1, s)) return rc;
+  // the table: one descriptor per circuit (table offset, instances, trace row 0, used rows),
+  // then per circuit its n_c + 1 instance starts rebased to its row 0 and its n_c pool offsets
+  const uint32_t dw = perm_circ_words();
+  const size_t m = (size_t)dw * n_circuits + 2 * (i1 - i0) + n_circuits;
+  uint64_t* it = nullptr;
+  if (int rc = perm_stage(ctx, m, &it)) return rc;
+  size_t at = (size_t)dw * n_circuits;
+  for (uint32_t c = 0; c < n_circuits; c++) {
+    const size_t a = h_circuit_first[c], b = h_circuit_first[c + 1], nc = b - a;
+    const uint64_t row0 = h_offsets[a];
+    it[(size_t)dw * c + 0] = at;
+    it[(size_t)dw * c + 1] = nc;
+    it[(size_t)dw * c + 2] = row0;
+    it[(size_t)dw * c + 3] = h_offsets[b] - row0;
+    for (size_t i = 0; i <= nc; i++) it[at + i] = h_offsets[a + i] - row0;
+    for (size_t i = 0; i < nc; i++) it[at + nc + 1 + i] = ctx->pm_pool_off[need[a + i]];
+    at += 2 * nc + 1;
+  }
+  // circuits per pass: the scratch holds one group's column sets, whatever n_circuits is
+  const uint32_t group = perm_batch_group(usable_rows, n_circuits, chunk_len);
+  if (int rc = perm_upload(ctx, m, perm_batch_scratch_bytes(k, usable_rows, group, chunk_len), s)) return rc;
+  if (int rc = ensure_side(ctx)) return rc;
+  int tk = timed_begin(ctx, B2F_KERNEL_PERM, s);
+  HIPCHK(ctx, launch_permutation_batch(d_advice, total_rows, ctx->d_pm_inst, n_circuits, group,
+                                       ctx->d_pm_pool, k, usable_rows, omega, delta, beta, gamma, chunk_len,
+                                       form, d_z, out_rows, ctx->d_pm, ctx->d_status + 2, ctx->s2,
+                                       ctx->ev_fork, ctx->ev_join, s));
   timed_end(ctx, tk, s);
   return B2F_OK;
 }

@@ -36,6 +36,16 @@ hipError_t launch_permutation(const uint32_t* d_advice, uint64_t total_rows, uin
                               uint32_t chunk_len, uint32_t form, uint64_t* d_sigma, uint64_t* d_z,
                               uint64_t out_rows, void* scratch, int* sticky, hipStream_t s2,
                               hipEvent_t ev_fork, hipEvent_t ev_join, hipStream_t s);
+size_t perm_batch_scratch_bytes(uint32_t k, uint64_t usable_rows, uint32_t group, uint32_t chunk_len);
+uint32_t perm_batch_group(uint64_t usable_rows, uint32_t n_circuits, uint32_t chunk_len);
+uint32_t perm_circ_words();
+hipError_t launch_permutation_batch(const uint32_t* d_advice, uint64_t total_rows, const uint64_t* d_tab,
+                                    uint32_t n_circuits, uint32_t group, const uint32_t* d_pool,
+                                    uint32_t k, uint64_t usable_rows, const uint64_t* omega,
+                                    const uint64_t* delta, const uint64_t* beta, const uint64_t* gamma,
+                                    uint32_t chunk_len, uint32_t form, uint64_t* d_z, uint64_t out_rows,
+                                    void* scratch, int* sticky, hipStream_t s2, hipEvent_t ev_fork,
+                                    hipEvent_t ev_join, hipStream_t s);
 
 namespace {
 
@@ -98,6 +108,27 @@ struct Inst {
   uint32_t n;
 };
 
+// A batch of circuits (b2f_permutation_columns_batch_dev): the device table starts with one
+// descriptor per circuit -- CIRC_WORDS u64: the table offset (u64 units) of the circuit's n + 1
+// instance starts (rebased to its row 0) followed by its n pool offsets, n, the trace row of its
+// row 0, and its used rows. Circuit c of a launch is blockIdx.z (+ the group's first circuit), so
+// the descriptor and everything read through it are scalar loads, uniform over the workgroup.
+constexpr uint32_t CIRC_WORDS = 4;
+struct Circ {
+  Inst I;
+  uint64_t row0, used;
+};
+__device__ __forceinline__ Circ circ_of(const uint64_t* __restrict__ tab, uint32_t c) {
+  const uint64_t* d = tab + (uint64_t)CIRC_WORDS * c;
+  Circ C;
+  C.I.start = tab + d[0];
+  C.I.n = (uint32_t)d[1];
+  C.I.pat = C.I.start + C.I.n + 1;
+  C.row0 = d[2];
+  C.used = d[3];
+  return C;
+}
+
 // the instance holding row r of a wave whose first row is `base` (wave-uniform: one search per
 // wave, scalar loads), then a lane's forward steps past the instance starts up to its row (an
 // instance has at least 228 rows, so a 64-row wave crosses at most one start)
@@ -155,27 +186,27 @@ __global__ __launch_bounds__(256) void pm_sigma_kernel(Inst I, const uint32_t* _
 // num/den of every column set for rows r < usable: a wave per 64 rows (the instance lookup and
 // the cell loads shared by the sets), the factors stored through LDS to their slots
 // (gp::wave_store_slots, non-temporal)
+// (`set`: the column set, columns [j0, j1); `y`: the product's slice of num / den -- the set
+// for one circuit, circuit * sets + set for a batch)
 template <class F>
-__global__ __launch_bounds__(256) void pm_factor_kernel(Inst I, const uint32_t* __restrict__ pool,
-                                                        const uint32_t* __restrict__ adv,
-                                                        uint64_t total_rows, uint64_t row0,
-                                                        uint64_t usable, uint32_t chunk_len,
-                                                        const Fe* __restrict__ BL,
-                                                        const Fe* __restrict__ OH, const Fe* __restrict__ G,
-                                                        Fe* __restrict__ num, Fe* __restrict__ den) {
+__device__ __forceinline__ void pm_factor_body(const Inst& I, const uint32_t* __restrict__ pool,
+                                               const uint32_t* __restrict__ adv, uint64_t total_rows,
+                                               uint64_t row0, uint64_t used, uint64_t usable,
+                                               uint32_t chunk_len, const Fe* __restrict__ BL,
+                                               const Fe* __restrict__ OH, const Fe* __restrict__ G,
+                                               Fe* __restrict__ num, Fe* __restrict__ den, uint32_t set,
+                                               uint32_t y) {
   __shared__ uint4 stage[4][128];
   const uint32_t lane = threadIdx.x & 63u, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint64_t base = (uint64_t)blockIdx.x * 256 + 64 * wv;
   if (base >= usable) return;
   const uint64_t r0 = base + lane;
   const uint64_t r = r0 < usable ? r0 : base;  // lanes past the end repeat row base (slots unused)
-  const uint32_t set = blockIdx.y;  // column set: columns [j0, j1)
   const uint32_t j0 = set * chunk_len, j1 = j0 + chunk_len < (uint32_t)NCOL ? j0 + chunk_len : NCOL;
-  num += (uint64_t)set * gp::elems(usable);
-  den += (uint64_t)set * gp::elems(usable);
+  num += (uint64_t)y * gp::elems(usable);
+  den += (uint64_t)y * gp::elems(usable);
   const Fe gamma = G[0];
   const uint32_t ii = inst_of_wave(I, base, r);
-  const uint64_t used = I.start[I.n];
   Fe n, d;  // the first column's factors, then one product per further column
 #pragma unroll 1
   for (uint32_t j = j0; j < j1; j++) {
@@ -195,6 +226,31 @@ __global__ __launch_bounds__(256) void pm_factor_kernel(Inst I, const uint32_t* 
   gp::wave_store_slots<true>(num + sb, stage[wv], lane, n);
   gp::wave_store_slots<true>(den + sb, stage[wv], lane, d);
 }
+template <class F>
+__global__ __launch_bounds__(256) void pm_factor_kernel(Inst I, const uint32_t* __restrict__ pool,
+                                                        const uint32_t* __restrict__ adv,
+                                                        uint64_t total_rows, uint64_t row0,
+                                                        uint64_t usable, uint32_t chunk_len,
+                                                        const Fe* __restrict__ BL,
+                                                        const Fe* __restrict__ OH, const Fe* __restrict__ G,
+                                                        Fe* __restrict__ num, Fe* __restrict__ den) {
+  pm_factor_body<F>(I, pool, adv, total_rows, row0, I.start[I.n], usable, chunk_len, BL, OH, G, num, den,
+                    blockIdx.y, blockIdx.y);
+}
+// the batched form: grid (row blocks, sets, circuits of the group), circuit c0 + blockIdx.z
+template <class F>
+__global__ __launch_bounds__(256) void pm_factor_batch_kernel(const uint64_t* __restrict__ tab, uint32_t c0,
+                                                              const uint32_t* __restrict__ pool,
+                                                              const uint32_t* __restrict__ adv,
+                                                              uint64_t total_rows, uint64_t usable,
+                                                              uint32_t chunk_len, const Fe* __restrict__ BL,
+                                                              const Fe* __restrict__ OH,
+                                                              const Fe* __restrict__ G, Fe* __restrict__ num,
+                                                              Fe* __restrict__ den) {
+  const Circ C = circ_of(tab, c0 + blockIdx.z);
+  pm_factor_body<F>(C.I, pool, adv, total_rows, C.row0, C.used, usable, chunk_len, BL, OH, G, num, den,
+                    blockIdx.y, blockIdx.z * gridDim.y + blockIdx.y);
+}
 
 constexpr uint32_t PM_CL = 3;  // pm_chunk_kernel's column sets: chunk_len <= 3 (halo2's usual 3)
 // waves per SIMD pm_chunk_kernel is compiled for: BN254 fits 4 (119 VGPRs, no scratch; 147 at
@@ -210,26 +266,26 @@ template <> struct PmWaves<field::Bn254> { static constexpr int v = B2F_PM_WAVES
 // to den (gp::slot_of, non-temporal) -- then the workgroup's block scan (gp::block_scan). The
 // factors never make the round trip through HBM that pm_factor_kernel -> gp_chunk took (64
 // bytes written, 64 read and 32 rewritten per row and set).
+// `set`: the column set; `y` of `g`: the product (its num / den slice and its place in the grand
+// product's scratch) -- the set of `sets` for one circuit, circuit * sets + set of group * sets
+// for a batch.
 template <class F>
-__global__ __launch_bounds__(gp::BLK) __attribute__((amdgpu_waves_per_eu(PmWaves<F>::v))) void pm_chunk_kernel(Inst I, const uint32_t* __restrict__ pool,
-                                                           const uint32_t* __restrict__ adv,
-                                                           uint64_t total_rows, uint64_t row0,
-                                                           uint64_t usable, uint32_t chunk_len,
-                                                           const Fe* __restrict__ BL,
-                                                           const Fe* __restrict__ OH,
-                                                           const Fe* __restrict__ G,
-                                                           Fe* __restrict__ num, Fe* __restrict__ den,
-                                                           Fe* __restrict__ zs) {
+__device__ __forceinline__ void pm_chunk_body(const Inst& I, const uint32_t* __restrict__ pool,
+                                              const uint32_t* __restrict__ adv, uint64_t total_rows,
+                                              uint64_t row0, uint64_t used, uint64_t usable,
+                                              uint32_t chunk_len, const Fe* __restrict__ BL,
+                                              const Fe* __restrict__ OH, const Fe* __restrict__ G,
+                                              Fe* __restrict__ num, Fe* __restrict__ den,
+                                              Fe* __restrict__ zs, uint32_t set, uint32_t y, uint32_t g) {
   __shared__ Fe sn[gp::BLK], sd[gp::BLK];
-  const uint32_t t = threadIdx.x, set = blockIdx.y, sets = gridDim.y;
+  const uint32_t t = threadIdx.x;
   const uint32_t j0 = set * chunk_len, j1 = j0 + chunk_len < (uint32_t)NCOL ? j0 + chunk_len : NCOL;
   const uint64_t nq = gp::n_chunks(usable), nb = gp::n_blocks(usable);
-  const gp::Scratch k = gp::scratch_of(zs, sets, usable);
-  Fe* nm = num + (uint64_t)set * gp::elems(usable);
-  Fe* dn = den + (uint64_t)set * gp::elems(usable);
+  const gp::Scratch k = gp::scratch_of(zs, g, usable);
+  Fe* nm = num + (uint64_t)y * gp::elems(usable);
+  Fe* dn = den + (uint64_t)y * gp::elems(usable);
   const uint64_t q = (uint64_t)blockIdx.x * gp::BLK + t;
   const Fe gamma = G[0];
-  const uint64_t used = I.start[I.n];
   Fe pn = field::one<F>(), pd = field::one<F>();
   {
     // the wave's first row -> its instance (one search per wave), then this lane's first row
@@ -318,7 +374,33 @@ __global__ __launch_bounds__(gp::BLK) __attribute__((amdgpu_waves_per_eu(PmWaves
     }
 #undef PM_FETCH
   }
-  gp::block_scan<F>(sn, sd, t, q, nq, nb, set, pn, pd, k.zn, k.zd, k.tn, k.td);
+  gp::block_scan<F>(sn, sd, t, q, nq, nb, y, pn, pd, k.zn, k.zd, k.tn, k.td);
+}
+template <class F>
+__global__ __launch_bounds__(gp::BLK) __attribute__((amdgpu_waves_per_eu(PmWaves<F>::v))) void pm_chunk_kernel(Inst I, const uint32_t* __restrict__ pool,
+                                                           const uint32_t* __restrict__ adv,
+                                                           uint64_t total_rows, uint64_t row0,
+                                                           uint64_t usable, uint32_t chunk_len,
+                                                           const Fe* __restrict__ BL,
+                                                           const Fe* __restrict__ OH,
+                                                           const Fe* __restrict__ G,
+                                                           Fe* __restrict__ num, Fe* __restrict__ den,
+                                                           Fe* __restrict__ zs) {
+  pm_chunk_body<F>(I, pool, adv, total_rows, row0, I.start[I.n], usable, chunk_len, BL, OH, G, num, den, zs,
+                   blockIdx.y, blockIdx.y, gridDim.y);
+}
+// The batched form: grid (blocks, sets, circuits of the group), circuit c0 + blockIdx.z of the
+// table; product blockIdx.z * sets + set of the group's gridDim.z * sets. Same body, same
+// occupancy target.
+template <class F>
+__global__ __launch_bounds__(gp::BLK) __attribute__((amdgpu_waves_per_eu(PmWaves<F>::v))) void pm_chunk_batch_kernel(
+    const uint64_t* __restrict__ tab, uint32_t c0, const uint32_t* __restrict__ pool,
+    const uint32_t* __restrict__ adv, uint64_t total_rows, uint64_t usable, uint32_t chunk_len,
+    const Fe* __restrict__ BL, const Fe* __restrict__ OH, const Fe* __restrict__ G, Fe* __restrict__ num,
+    Fe* __restrict__ den, Fe* __restrict__ zs) {
+  const Circ C = circ_of(tab, c0 + blockIdx.z);
+  pm_chunk_body<F>(C.I, pool, adv, total_rows, C.row0, C.used, usable, chunk_len, BL, OH, G, num, den, zs,
+                   blockIdx.y, blockIdx.z * gridDim.y + blockIdx.y, gridDim.y * gridDim.z);
 }
 
 struct Carve {
@@ -396,6 +478,44 @@ hipError_t run_perm(const uint32_t* d_advice, uint64_t total_rows, uint64_t row0
   return hipGetLastError();
 }
 
+// Products a grid's y dimension holds (gp_chunk, gp_write: one product per blockIdx.y).
+constexpr uint32_t MAX_PRODUCTS = 65535;
+
+// The z columns of n_circuits circuits (d_tab: their descriptors and instance tables), `group`
+// circuits per pass: the coset tables and gamma once, then per group the factors of all its
+// circuits' column sets in one launch and group * sets grand products side by side, chained
+// within each circuit. The scratch is carved for one group and reused by the next (stream order).
+template <class F>
+hipError_t run_perm_batch(const uint32_t* d_advice, uint64_t total_rows, const uint64_t* d_tab,
+                          uint32_t n_circuits, uint32_t group, const uint32_t* d_pool, uint32_t k,
+                          uint64_t usable, const Params& prm, uint32_t chunk_len, bool mont, uint64_t* d_z,
+                          uint64_t out_rows, void* scratch, int* sticky, gp::Side side, hipStream_t s) {
+  const uint32_t sets = (NCOL + chunk_len - 1) / chunk_len;
+  Carve m = carve(scratch, k, usable, sets * group);
+  const uint64_t n_rows = 1ull << k, n_hi = n_rows / LO;
+  const uint64_t tab = n_hi > (uint64_t)NCOL * LO ? n_hi : (uint64_t)NCOL * LO;
+  hipLaunchKernelGGL(pm_table_kernel<F>, dim3((uint32_t)((tab + 255) / 256)), dim3(256), 0, s, prm,
+                     n_hi, m.OL, m.BL, m.OH, m.gm);
+  const bool fused = chunk_len <= PM_CL;
+  for (uint32_t c0 = 0; c0 < n_circuits; c0 += group) {
+    const uint32_t cnt = n_circuits - c0 < group ? n_circuits - c0 : group, g = cnt * sets;
+    if (fused)
+      hipLaunchKernelGGL(pm_chunk_batch_kernel<F>, dim3((uint32_t)gp::n_blocks(usable), sets, cnt),
+                         dim3(gp::BLK), 0, s, d_tab, c0, d_pool, d_advice, total_rows, usable, chunk_len,
+                         m.BL, m.OH, m.gm, m.num, m.den, m.zs);
+    else
+      hipLaunchKernelGGL(pm_factor_batch_kernel<F>, dim3((uint32_t)((usable + 255) / 256), sets, cnt),
+                         dim3(256), 0, s, d_tab, c0, d_pool, d_advice, total_rows, usable, chunk_len, m.BL,
+                         m.OH, m.gm, m.num, m.den);
+    hipError_t e = gp::run_begin<F>(g, usable, m.num, m.den, m.zs, sticky, side, s, fused);
+    if (e != hipSuccess) return e;
+    e = gp::run_end<F>(g, usable, mont, d_z + (uint64_t)c0 * sets * out_rows * 4, out_rows * 4, m.num,
+                       m.den, m.zs, nullptr, nullptr, s, m.seed, side, sets);
+    if (e != hipSuccess) return e;
+  }
+  return hipGetLastError();
+}
+
 // keygen: the sigma columns alone (the tables they read, then pm_sigma_kernel)
 template <class F>
 hipError_t run_perm_sigma(const Inst& I, const uint32_t* d_pool, uint32_t k, const Params& prm, bool mont,
@@ -463,6 +583,50 @@ hipError_t launch_permutation(const uint32_t* d_advice, uint64_t total_rows, uin
                                   chunk_len, mont, d_sigma, d_z, out_rows, scratch, sticky, side, s);
   return run_perm<field::Pallas>(d_advice, total_rows, row0, I, d_pool, k, usable_rows, prm, gamma,
                                  chunk_len, mont, d_sigma, d_z, out_rows, scratch, sticky, side, s);
+}
+
+// circuits per pass of the batch call: the lookup call's rule (at most 2^24 rows, enough
+// workgroups to fill the chip several times over), and no more products than a grid's y holds
+uint32_t perm_batch_group(uint64_t usable_rows, uint32_t n_circuits, uint32_t chunk_len) {
+  const uint32_t sets = (NCOL + chunk_len - 1) / chunk_len;
+  uint64_t group = (1ull << 24) / (usable_rows ? usable_rows : 1);
+  if (group > MAX_PRODUCTS / sets) group = MAX_PRODUCTS / sets;
+  if (group < 1) group = 1;
+  if (group > n_circuits) group = n_circuits;
+  return (uint32_t)group;
+}
+
+uint32_t perm_circ_words() { return CIRC_WORDS; }
+
+size_t perm_batch_scratch_bytes(uint32_t k, uint64_t usable_rows, uint32_t group, uint32_t chunk_len) {
+  return carve(nullptr, k, usable_rows, group * ((NCOL + chunk_len - 1) / chunk_len)).total;
+}
+
+// d_tab: CIRC_WORDS u64 per circuit (table offset, instances, trace row 0, used rows), then every
+// circuit's n + 1 rebased instance starts and n pool offsets
+hipError_t launch_permutation_batch(const uint32_t* d_advice, uint64_t total_rows, const uint64_t* d_tab,
+                                    uint32_t n_circuits, uint32_t group, const uint32_t* d_pool,
+                                    uint32_t k, uint64_t usable_rows, const uint64_t* omega,
+                                    const uint64_t* delta, const uint64_t* beta, const uint64_t* gamma,
+                                    uint32_t chunk_len, uint32_t form, uint64_t* d_z, uint64_t out_rows,
+                                    void* scratch, int* sticky, hipStream_t s2, hipEvent_t ev_fork,
+                                    hipEvent_t ev_join, hipStream_t s) {
+  const gp::Side side{s2, ev_fork, ev_join};
+  Params prm;
+  for (int i = 0; i < 4; i++) {
+    prm.omega[i] = omega[i];
+    prm.delta[i] = delta[i];
+    prm.beta[i] = beta[i];
+    prm.gamma[i] = gamma[i];
+  }
+  const bool mont = (form & 1u) != 0;
+  if (form >> 1)
+    return run_perm_batch<field::Bn254>(d_advice, total_rows, d_tab, n_circuits, group, d_pool, k,
+                                        usable_rows, prm, chunk_len, mont, d_z, out_rows, scratch, sticky,
+                                        side, s);
+  return run_perm_batch<field::Pallas>(d_advice, total_rows, d_tab, n_circuits, group, d_pool, k,
+                                       usable_rows, prm, chunk_len, mont, d_z, out_rows, scratch, sticky,
+                                       side, s);
 }
 
 }  // namespace b2f
