@@ -55,7 +55,8 @@ extern "C" {
 #define B2F_ERR_LAYOUT 5    /* offsets are not the prefix sums of R(rounds_i) */
 #define B2F_ERR_INPUT 6     /* malformed EIP-152 input (length != 213 or f not 0/1) */
 #define B2F_ERR_FIELD 7     /* (at b2f_sync) a grand product's denominator product is zero: a
-                               challenge collides with a cell value, its z column is meaningless */
+                               challenge collides with a cell value, its z column is meaningless;
+                               or an NTT's omega is not a primitive 2^k-th root of unity */
 #define B2F_ERR_CHECK 8     /* (at b2f_sync) an internal cross-check failed -- a library defect:
                                the lookup's permuted columns do not multiply to the product of
                                its input columns (its columns are wrong), or the fused pass's
@@ -189,7 +190,7 @@ B2F_API uint64_t b2f_copy_constraints(uint32_t rounds, uint32_t* out4, uint64_t 
 
 /* Wait for `stream` and return the first device-side error of the calls issued since the
  * previous b2f_sync (B2F_ERR_LAYOUT / B2F_ERR_ROUNDS from fill/eval, B2F_ERR_FIELD from the
- * lookup / permutation grand products), then clear it. */
+ * lookup / permutation grand products and the NTT's root check), then clear it. */
 B2F_API int b2f_sync(b2f_ctx* ctx, void* stream);
 
 /* Host-pointer conveniences (allocate, copy, run, copy back; blocking). b2f_fill sizes the
@@ -353,6 +354,39 @@ B2F_API int b2f_permutation_sigma_dev(b2f_ctx* ctx, const uint64_t* h_offsets, s
                                       const uint64_t omega[4], const uint64_t delta[4], uint32_t form,
                                       uint64_t* d_sigma, uint64_t out_rows, void* stream);
 
+/* Batched NTT of prover columns (halo2's EvaluationDomain::lagrange_to_coeff, coeff_to_lagrange
+ * and coeff_to_extended), n = 2^k rows, n_cols columns in one call. Column c of the input is
+ * d_in[(c * in_rows + i) * 4 + limb] (the layout every prover-column call here writes): rows
+ * i < in_len are read, rows in_len .. n - 1 are taken as zero (coeff_to_extended's padding, no
+ * padded copy) and never read. Column c of the output is d_out[(c * out_rows + i) * 4 + limb]:
+ * all n rows are written in natural order, rows >= n are not touched. omega (the generator of the
+ * 2^k domain) and shift (non-zero) are canonical elements of the field `form` selects (any
+ * B2F_FP_*); data is in `form` on both sides, inputs reduced (< p), outputs fully reduced.
+ *   B2F_NTT_FORWARD  out[i] = sum_j in[j] (shift omega^i)^j: coefficients to evaluations on the
+ *                    coset shift <omega>. shift = 1 is coeff_to_lagrange; coeff_to_extended is
+ *                    k = the extended k, in_len = 2^k_circuit, shift = F::ZETA.
+ *   B2F_NTT_INVERSE  out[j] = shift^-j n^-1 sum_i in[i] omega^(-i j): the exact inverse of the
+ *                    forward map for the same omega and shift. shift = 1 is lagrange_to_coeff.
+ * The caller passes the domain's own omega and shift in both directions; omega^-1, n^-1 and
+ * shift^-1 are derived on the device. Twiddle and shift-power tables are built on the device once
+ * per (field, k, direction, omega, shift) and cached in the context (8 domains, replaced
+ * round-robin), so a repeated call builds nothing.
+ * B2F_ERR_ARG: a null pointer, d_in or d_out not 16-byte aligned, k outside [1, 28] (BN254's
+ * 2-adicity; one limit for both fields), n_cols == 0, in_len == 0, direction > 1, form > 3, omega
+ * or shift >= p, shift == 0, or any overlap of [d_in, d_in + n_cols in_rows 32) with
+ * [d_out, d_out + n_cols out_rows 32) (no in-place transform). B2F_ERR_ROWS: in_len > 2^k,
+ * in_rows < in_len or out_rows < 2^k. Nothing is launched on either. B2F_ERR_FIELD at b2f_sync
+ * when omega^(2^(k-1)) != -1 (omega is not a primitive 2^k-th root of unity): the outputs are then
+ * meaningless; the next call works normally. Asynchronous on `stream`; one call is one
+ * B2F_KERNEL_NTT region. n_cols may exceed 65,535 (the call launches column groups). */
+#define B2F_NTT_FORWARD 0
+#define B2F_NTT_INVERSE 1
+B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_rows,
+                                uint64_t in_len, uint32_t n_cols, uint32_t k,
+                                const uint64_t omega[4], const uint64_t shift[4],
+                                uint32_t direction, uint32_t form, uint64_t* d_out,
+                                uint64_t out_rows, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream around every kernel the
  * fill/eval calls launch (no host synchronization while recording). b2f_set_timing(ctx, 1)
  * clears the log and starts recording; b2f_kernel_times waits for the recorded events and
@@ -366,9 +400,11 @@ B2F_API int b2f_permutation_sigma_dev(b2f_ctx* ctx, const uint64_t* h_offsets, s
 #define B2F_KERNEL_LOOKUP 5 /* lookup-argument prover columns (all passes of one call) */
 #define B2F_KERNEL_PERM 6   /* permutation-argument prover columns (all passes of one call) */
 #define B2F_KERNEL_PERM_SIGMA 7 /* permutation keygen: the sigma columns (b2f_permutation_sigma_dev) */
-#define B2F_NUM_KERNELS 8
+#define B2F_KERNEL_NTT 8    /* NTT of prover columns (table build and all passes of one call) */
+#define B2F_NUM_KERNELS 9
 /* total_ms and count must each hold b2f_num_kernels() entries (= B2F_NUM_KERNELS of the
- * header the library was built with; it grew from 7 to 8 with B2F_KERNEL_PERM_SIGMA): a caller
+ * header the library was built with; it grew from 7 to 8 with B2F_KERNEL_PERM_SIGMA and to 9
+ * with B2F_KERNEL_NTT): a caller
  * built against another header sizes its buffers from the query, so the library never writes
  * past them. */
 B2F_API int b2f_num_kernels(void);

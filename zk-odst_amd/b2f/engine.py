@@ -204,6 +204,44 @@ class Engine:
             self.ctx, _np_ptr(off), len(off) - 1, int(k), lim[0], lim[1], int(form), _vp(d_sigma),
             int(out_rows), _vp(stream)))
 
+    def ntt_columns_dev(self, d_in, in_rows, in_len, n_cols, k, omega, shift, direction, form,
+                        d_out, out_rows, stream=0):
+        """b2f_ntt_columns_dev; omega/shift are Python ints (canonical)."""
+        lim = [(ctypes.c_uint64 * 4)(*[(int(v) >> (64 * i)) & (2**64 - 1) for i in range(4)])
+               for v in (omega, shift)]
+        self._check(self.lib.b2f_ntt_columns_dev(
+            self.ctx, _vp(d_in), int(in_rows), int(in_len), int(n_cols), int(k), lim[0], lim[1],
+            int(direction), int(form), _vp(d_out), int(out_rows), _vp(stream)))
+
+    def ntt_columns(self, cols, k, inverse=False, shift=1, in_len=None, form=_lib.FP_MONTGOMERY,
+                    out=None, stream=None):
+        """NTT of every column of `cols`, a contiguous int64 [n_cols, rows, 4] tensor of field
+        elements in `form`, over the 2^k domain of the form's field: forward (coefficients to
+        evaluations on the coset shift <omega>; rows in_len .. 2^k - 1 count as zero) or inverse.
+        Returns int64 [n_cols, 2^k, 4] (`out`, when given: contiguous int64 [n_cols, rows >= 2^k,
+        4], rows past 2^k untouched) -- see b2f_ntt_columns_dev."""
+        import torch
+
+        from . import field
+
+        if cols.dim() != 3 or cols.shape[2] != 4 or cols.dtype != torch.int64 \
+                or not cols.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "ntt_columns: cols must be contiguous int64 [n_cols, rows, 4]")
+        n_cols, rows = int(cols.shape[0]), int(cols.shape[1])
+        n = 1 << int(k)
+        in_len = min(rows, n) if in_len is None else int(in_len)
+        if out is None:
+            out = torch.empty((n_cols, n, 4), dtype=torch.int64, device=cols.device)
+        if out.dim() != 3 or out.shape[0] != n_cols or out.shape[2] != 4 \
+                or out.dtype != torch.int64 or not out.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "ntt_columns: out must be contiguous int64 [n_cols, rows, 4]")
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.ntt_columns_dev(cols.data_ptr(), rows, in_len, n_cols, k,
+                             field.omega(field.of_form(form), int(k)), shift,
+                             _lib.NTT_INVERSE if inverse else _lib.NTT_FORWARD, form,
+                             out.data_ptr(), int(out.shape[1]), s)
+        return out
+
     def debug_eval_path(self):
         """Path of the last eval_dev call (device-synchronizing): 0 the fast clean-check pass
         found the trace clean, 1 it flagged something and the exact eval kernel reported, 2 no

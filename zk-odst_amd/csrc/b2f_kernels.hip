@@ -65,6 +65,12 @@ hipError_t launch_permutation_batch(const uint32_t* d_advice, uint64_t total_row
                                     uint32_t chunk_len, uint32_t form, uint64_t* d_z, uint64_t out_rows,
                                     void* scratch, int* sticky, hipStream_t s2, hipEvent_t ev_fork,
                                     hipEvent_t ev_join, hipStream_t s);
+size_t ntt_table_bytes(uint32_t k);  // b2f_ntt.hip
+hipError_t launch_ntt_tables(void* d_tab, uint32_t form, uint32_t k, const uint64_t* omega,
+                             const uint64_t* shift, uint32_t direction, hipStream_t s);
+hipError_t launch_ntt(const uint64_t* d_in, uint64_t in_rows, uint64_t in_len, uint32_t n_cols,
+                      uint32_t k, uint32_t form, uint32_t direction, bool shift_is_one, uint64_t* d_out,
+                      uint64_t out_rows, const void* d_tab, int* sticky, hipStream_t s);
 hipError_t launch_export_fp(const uint32_t* d_advice, uint64_t total_rows, uint64_t row_begin,
                             uint64_t nrows, uint32_t form, uint64_t* d_out, uint64_t out_rows,
                             int cu_count, unsigned* tctr, hipStream_t s);  // b2f_export.hip
@@ -971,6 +977,19 @@ struct b2f_ctx {
   hipEvent_t ev_fork, ev_join;
   hipStream_t s3;                // the lookup's table pass and sort (beside the count pass)
   hipEvent_t ev_tab, ev_sorted;
+  // NTT twiddle / shift-power tables (b2f_ntt.hip), one block per (field, k, direction, omega,
+  // shift) seen, replaced round-robin: a prover alternates a few domains, and a repeated call
+  // builds nothing
+  struct NttTab {
+    uint32_t field, k, direction;
+    uint64_t omega[4], shift[4];
+    void* d;
+    size_t cap;
+    bool live;
+  };
+  static constexpr int NTT_TABS = 8;
+  NttTab ntt_tab[NTT_TABS];
+  uint32_t ntt_next;
 };
 
 namespace {
@@ -1247,6 +1266,7 @@ B2F_API void b2f_destroy(b2f_ctx* ctx) {
   (void)hipFree(ctx->d_pm_pool);
   (void)hipFree(ctx->d_pm_inst);
   (void)hipFree(ctx->d_pm);
+  for (auto& t : ctx->ntt_tab) (void)hipFree(t.d);
   if (ctx->pm_inst_ev_live) (void)hipEventSynchronize(ctx->pm_inst_ev);
   if (ctx->pm_inst_ev) (void)hipEventDestroy(ctx->pm_inst_ev);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
@@ -1940,6 +1960,77 @@ B2F_API int b2f_permutation_sigma_dev(b2f_ctx* ctx, const uint64_t* h_offsets, s
   return B2F_OK;
 }
 
+B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_rows,
+                                uint64_t in_len, uint32_t n_cols, uint32_t k,
+                                const uint64_t omega[4], const uint64_t shift[4],
+                                uint32_t direction, uint32_t form, uint64_t* d_out,
+                                uint64_t out_rows, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  if (!d_in || !d_out || !omega || !shift) return set_err(ctx, B2F_ERR_ARG, "ntt: null buffer");
+  if (((uintptr_t)d_in | (uintptr_t)d_out) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "ntt: buffers must be 16-byte aligned");
+  if (k < 1 || k > 28) return set_err(ctx, B2F_ERR_ARG, "ntt: k %u not in [1, 28]", k);
+  if (n_cols == 0 || in_len == 0) return set_err(ctx, B2F_ERR_ARG, "ntt: no columns or no input rows");
+  if (direction > B2F_NTT_INVERSE) return set_err(ctx, B2F_ERR_ARG, "ntt: unknown direction %u", direction);
+  if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "ntt: unknown form %u", form);
+  static const uint64_t moduli[2][4] = {
+      {0x992d30ed00000001ull, 0x224698fc094cf91bull, 0, 0x4000000000000000ull},
+      {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull}};
+  auto canon = [&](const uint64_t* v) {
+    const uint64_t* p = moduli[form >> 1];
+    for (int i = 3; i >= 0; i--)
+      if (v[i] != p[i]) return v[i] < p[i];
+    return false;
+  };
+  if (!canon(omega) || !canon(shift))
+    return set_err(ctx, B2F_ERR_ARG, "ntt: omega/shift not canonical field elements");
+  if (!(shift[0] | shift[1] | shift[2] | shift[3])) return set_err(ctx, B2F_ERR_ARG, "ntt: shift is zero");
+  const uint64_t n_rows = 1ull << k;
+  if (in_len > n_rows) return set_err(ctx, B2F_ERR_ROWS, "ntt: in_len %llu > 2^k", (unsigned long long)in_len);
+  if (in_rows < in_len) return set_err(ctx, B2F_ERR_ROWS, "ntt: in_rows < in_len");
+  if (out_rows < n_rows) return set_err(ctx, B2F_ERR_ROWS, "ntt: out_rows < 2^k");
+  if (in_rows > (1ull << 58) / n_cols || out_rows > (1ull << 58) / n_cols)
+    return set_err(ctx, B2F_ERR_ARG, "ntt: column strides overflow the address space");
+  const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (uint64_t)n_cols * in_rows * 32;
+  const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (uint64_t)n_cols * out_rows * 32;
+  if (i0 < o1 && o0 < i1) return set_err(ctx, B2F_ERR_ARG, "ntt: input and output overlap (no in-place transform)");
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // the table block of this domain: cached, or built into the next slot
+  b2f_ctx::NttTab* tab = nullptr;
+  for (auto& t : ctx->ntt_tab)
+    if (t.live && t.field == (form >> 1) && t.k == k && t.direction == direction &&
+        !memcmp(t.omega, omega, 32) && !memcmp(t.shift, shift, 32))
+      tab = &t;
+  int tk = timed_begin(ctx, B2F_KERNEL_NTT, s);
+  if (!tab) {
+    b2f_ctx::NttTab& t = ctx->ntt_tab[ctx->ntt_next++ % b2f_ctx::NTT_TABS];
+    t.live = false;
+    const size_t need = ntt_table_bytes(k);
+    if (need > t.cap) {  // earlier calls on the stream may still read the block
+      HIPCHK(ctx, hipStreamSynchronize(s));
+      if (t.d) HIPCHK(ctx, hipFree(t.d));
+      t.d = nullptr;
+      t.cap = 0;
+      HIPCHK(ctx, hipMalloc(&t.d, need));
+      t.cap = need;
+    }
+    HIPCHK(ctx, launch_ntt_tables(t.d, form, k, omega, shift, direction, s));
+    t.field = form >> 1;
+    t.k = k;
+    t.direction = direction;
+    memcpy(t.omega, omega, 32);
+    memcpy(t.shift, shift, 32);
+    t.live = true;
+    tab = &t;
+  }
+  const bool shift_is_one = shift[0] == 1 && !(shift[1] | shift[2] | shift[3]);
+  HIPCHK(ctx, launch_ntt(d_in, in_rows, in_len, n_cols, k, form, direction, shift_is_one, d_out, out_rows,
+                         tab->d, ctx->d_status + 2, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
 B2F_API int b2f_fill_fixed_dev(b2f_ctx* ctx, const uint64_t* d_offsets, size_t n,
                                uint64_t total_rows, uint32_t* d_fixed, void* stream) {
   if (!ctx) return B2F_ERR_ARG;
@@ -1982,7 +2073,8 @@ B2F_API int b2f_sync(b2f_ctx* ctx, void* stream) {
   if (bits & (1 << B2F_ERR_LAYOUT))
     return set_err(ctx, B2F_ERR_LAYOUT, "row offsets are not the LAYOUT v1 prefix sums");
   if (bits & (1 << B2F_ERR_FIELD))
-    return set_err(ctx, B2F_ERR_FIELD, "a grand product's denominator is zero (challenge collision)");
+    return set_err(ctx, B2F_ERR_FIELD, "a grand product's denominator is zero (challenge collision), or an NTT's "
+                                       "omega is not a primitive 2^k-th root of unity");
   if (bits & (1 << B2F_ERR_CHECK))
     return set_err(ctx, B2F_ERR_CHECK, "internal cross-check failed (lookup den product vs input side, or "
                                        "the fused pass's segment list overflowed)");
