@@ -17,8 +17,9 @@ $H $O -c -o f.o csrc/b2f_fused.hip &
 $H -c -o e.o csrc/b2f_export.hip &
 $H -c -o l.o csrc/b2f_lookup.hip &
 $H -c -o p.o csrc/b2f_perm.hip &
+$H -c -o n.o csrc/b2f_ntt.hip &
 wait
 mkdir -p $ROOT/zk-odst_amd/variants
-$H -shared -o $ROOT/zk-odst_amd/variants/libb2f_$N.so k.o f.o e.o l.o p.o
+$H -shared -o $ROOT/zk-odst_amd/variants/libb2f_$N.so k.o f.o e.o l.o p.o n.o
 rm -rf $T
 echo built zk-odst_amd/variants/libb2f_$N.so from $REV

@@ -12,7 +12,8 @@ $H $O -c -o $D/f.o csrc/b2f_fused.hip &
 $H -c -o $D/e.o csrc/b2f_export.hip &
 $H -c -o $D/l.o csrc/b2f_lookup.hip &
 $H -c -o $D/p.o csrc/b2f_perm.hip &
+$H -c -o $D/n.o csrc/b2f_ntt.hip &
 wait
-$H -shared -o variants/libb2f_$N.so $D/k.o $D/f.o $D/e.o $D/l.o $D/p.o
+$H -shared -o variants/libb2f_$N.so $D/k.o $D/f.o $D/e.o $D/l.o $D/p.o $D/n.o
 rm -rf $D
 echo built variants/libb2f_$N.so

@@ -4,6 +4,10 @@
 //   wave  : every wave owns whole instances (dynamic: a global counter), writing an instance's
 //           rows in steps of STEP quads (52 = one half-round of 4 G's) from row 0 to its end
 //   wavesI: the same with a static interleave (wave w takes instances w, w + W, ...)
+//   j     : (store_probe <n> j [reps]) the fused pass's order -- instances claimed by waves,
+//           line-owned half-round tiles, the edge rows afterwards -- with the junction lines
+//           split as the fused pass wrote them, final | init paired, all written whole, or
+//           paired with only the first tile's line owned
 // Build: hipcc -O3 --offload-arch=gfx950 -o tools/store_probe tools/store_probe.hip
 #include <hip/hip_runtime.h>
 
@@ -345,6 +349,72 @@ __global__ void __launch_bounds__((NC + 1) * 64) wave_spec(uint32_t* adv, uint64
   }
 }
 
+// the fused pass's store order with no compute, to bound what whole junction lines can gain: a
+// wave claims whole instances (41 init quads, 24 half-round tiles of 52 quads, 16 final quads per
+// column) and writes their half-round tiles with line-owned raw non-temporal buffer stores; once
+// the instances are claimed it writes edge rows, claimed 8 tiles at a time.
+//   VAR 0: the half-round tiles own the lines between them only; an edge tile is one instance's
+//          init and final regions, stored separately (three lines per instance and column are
+//          written in two parts by two waves)
+//   VAR 1: an edge tile is a boundary: final(b - 1) + init(b), one contiguous store per column
+//   VAR 2: every junction line whole: the first tile also takes the init quads of its first
+//          line, the last tile leaves the quads of its last line to the boundary store, which
+//          so begins and ends on a line
+//   VAR 3: VAR 1 with the first tile's line owned as in VAR 2 (last half-round | final still split)
+template <int VAR>
+__global__ void __launch_bounds__(256) fused_order_store(uint32_t* adv, uint64_t total_rows, uint32_t n,
+                                                         unsigned* ctr) {
+  constexpr uint32_t HRQ = 52, NHR = 24, IQ = 41, FQ = 16, RPI = 4 * (IQ + NHR * HRQ + FQ);
+  const uint32_t lane = threadIdx.x & 63u;
+  auto claim = [&](unsigned* c, uint32_t k) {
+    uint32_t v = 0;
+    if (lane == 0) v = atomicAdd(c, k);
+    return (uint32_t)__builtin_amdgcn_readfirstlane(v);
+  };
+  // nq quads from word index w of the trace (lanes past nq: out of the resource's range)
+  auto put = [&](uint64_t w, uint32_t nq, uint32_t tag) {
+    const uint64_t a = reinterpret_cast<uint64_t>(adv + w);
+    const i32x4 rsrc = {(int32_t)(uint32_t)a, (int32_t)(uint32_t)(a >> 32), (int32_t)(nq * 16u), 0x00020000};
+    probe_buffer_store(i32x4{(int32_t)lane, (int32_t)tag, VAR, 3}, rsrc, (int)(16 * lane), 0, 2);
+  };
+  // quads between word index w and the head of its 128-byte line
+  auto lq = [&](uint64_t w) { return (uint32_t)(reinterpret_cast<uint64_t>(adv + w) >> 4) & 7u; };
+  for (;;) {
+    const uint32_t i = claim(ctr, 1u);
+    if (i >= n) break;
+    for (uint32_t h = 0; h < NHR; h++) {
+      const uint64_t row0 = (uint64_t)i * RPI + 4 * IQ + 4 * HRQ * h;
+      const bool own_head = VAR >= 2 || h != 0, own_tail = VAR != 2 && h == NHR - 1;
+#pragma unroll
+      for (int c = 0; c < 11; c++) {
+        const uint64_t w = (uint64_t)c * total_rows + row0;
+        const uint32_t kc = own_head ? lq(w) : 0u, tc = own_tail ? 0u : lq(w + 4 * HRQ);
+        put(w - 4 * kc, HRQ + kc - tc, i);
+      }
+    }
+  }
+  const uint32_t n_edge = VAR == 0 ? n : n + 1;
+  for (;;) {
+    const uint32_t b0 = claim(ctr + 1, 8u);
+    if (b0 >= n_edge) break;
+    for (uint32_t b = b0; b < b0 + 8 && b < n_edge; b++) {
+#pragma unroll
+      for (int c = 0; c < 11; c++) {
+        const uint64_t w = (uint64_t)c * total_rows + (uint64_t)b * RPI;
+        if (VAR == 0) {
+          put(w, IQ, b);
+          put(w + RPI - 4 * FQ, FQ, b);
+        } else {
+          uint64_t lo = b ? w - 4 * FQ : w, hi = b < n ? w + 4 * IQ : w;
+          if (VAR == 2 && b) lo -= 4 * lq(lo);
+          if (VAR >= 2 && b < n) hi -= 4 * lq(hi);
+          put(lo, (uint32_t)(hi - lo) / 4, b);
+        }
+      }
+    }
+  }
+}
+
 int main(int argc, char** argv) {
   const uint32_t n = argc > 1 ? atoi(argv[1]) : (1u << 18);
   const uint32_t rows_per = 228 + 416 * 12;
@@ -376,6 +446,39 @@ int main(int argc, char** argv) {
     fflush(stdout);
   };
   const uint64_t nt = (total + 1023) / 1024;
+  if (argc > 2 && argv[2][0] == 'j') {  // junction lines in the fused order: split / paired / whole / head,
+                                        // interleaved rep by rep, 3 workgroups per CU as the fused launch
+    CHK(hipFree(ctr));
+    CHK(hipMalloc(&ctr, 8));
+    const int reps = argc > 3 ? atoi(argv[3]) : 7;
+    const char* names[4] = {"fused_order_split", "fused_order_final_init_paired", "fused_order_whole_lines",
+                            "fused_order_paired_head_owned"};
+    float ms[4][16];
+    for (int rep = 0; rep < reps && rep < 16; rep++)
+      for (int v = 0; v < 4; v++) {
+        CHK(hipMemset(ctr, 0, 8));
+        CHK(hipEventRecord(a));
+        if (v == 0) hipLaunchKernelGGL(fused_order_store<0>, dim3(cus * 3), dim3(256), 0, 0, adv, total, n, ctr);
+        if (v == 1) hipLaunchKernelGGL(fused_order_store<1>, dim3(cus * 3), dim3(256), 0, 0, adv, total, n, ctr);
+        if (v == 2) hipLaunchKernelGGL(fused_order_store<2>, dim3(cus * 3), dim3(256), 0, 0, adv, total, n, ctr);
+        if (v == 3) hipLaunchKernelGGL(fused_order_store<3>, dim3(cus * 3), dim3(256), 0, 0, adv, total, n, ctr);
+        CHK(hipEventRecord(b));
+        CHK(hipEventSynchronize(b));
+        CHK(hipEventElapsedTime(&ms[v][rep], a, b));
+      }
+    for (int v = 0; v < 4; v++) {  // the first rep carries the warm-up: listed, not in min / max
+      float lo = 1e30f, hi = 0;
+      printf("{\"pattern\": \"%s\", \"n\": %u, \"ms_all\": [", names[v], n);
+      for (int rep = 0; rep < reps && rep < 16; rep++) {
+        printf("%s%.3f", rep ? ", " : "", ms[v][rep]);
+        if (rep && ms[v][rep] < lo) lo = ms[v][rep];
+        if (rep && ms[v][rep] > hi) hi = ms[v][rep];
+      }
+      printf("], \"ms_min\": %.3f, \"ms_max\": %.3f, \"TBs\": %.3f}\n", lo, hi, bytes / lo / 1e9);
+    }
+    CHK(hipGetLastError());
+    return 0;
+  }
   if (argc > 2 && argv[2][0] == 's') {  // wave-specialised store waves vs the burst pattern
     for (int work : {0, 120, 240}) {
       char nm[96];

@@ -270,9 +270,10 @@ __device__ __forceinline__ void producer_words(uint64_t* prod, const Ops& P, uin
 // MODE (diagnostics; the product launches FZ_FULL, with FZ_INJECT only under the test hook)
 #ifndef B2F_FUSED_WAVES
 // minimum waves per SIMD the half-round kernel is compiled for: 2, i.e. a VGPR ceiling of 256.
-// The kernel allocates 159 VGPRs, which leaves room for 3 waves per SIMD, and the launch runs
+// The kernel allocates 167 VGPRs, which leaves room for 3 waves per SIMD, and the launch runs
 // B2F_FUSED_HR_PER_CU = 3 workgroups (of 4 waves) per CU: 3 waves per SIMD. (Forcing a budget
-// of 3 per SIMD at compile time is not needed while the allocation stays <= 168.)
+// of 3 per SIMD at compile time is not needed while the allocation stays <= 168: check `make
+// resource-usage` after any change to the tile loop.)
 #define B2F_FUSED_WAVES 2
 #endif
 #ifndef B2F_FUSED_HR_PER_CU
@@ -1364,6 +1365,48 @@ fused_hr_kernel(const b2f_input* __restrict__ in, uint32_t n, const uint64_t* __
         put(A9, carry & K.madd, 0u, 0u, 0u);
         put(FXC, K.fx0, 0u, 0u, 0u);
       }
+      if (c.hr == 0 && tlane) {
+        // An instance's first tile has no previous tile (its tail lanes staged nothing of use
+        // above; this comes after it, when the tile's operands are dead): the rows in front of it are the init
+        // region's last seven quads -- quad 34 (CONST IV_7) and quads 35-40 (XOR: v12..v14 =
+        // IV_4..6 ^ t0, t1, fmask; two quads per word) -- and the tail lanes form those, so this
+        // tile's stores begin at a line head like every other tile's. The edge tile stages and
+        // checks the same quads and leaves the store of the last kc of them to this tile.
+        uint32_t e = lane - TAIL0;  // 0: the CONST quad, 1-6: XOR quad e - 1
+        // opaque: nothing derived from the lane's position here is hoisted out of the tile loop
+        // and kept in registers across it (the loop is at the budget of 3 waves per SIMD)
+        asm volatile("" : "+v"(e));
+        const uint32_t xa = e ? (e - 1u) >> 1 : 0u, hiw = e ? (e - 1u) & 1u : 0u;  // XOR word, its half
+        const uint64_t fw = INW[26];
+        const uint64_t Xi = e ? IV[4 + xa] : IV[7];
+        const uint64_t Yi = e == 0 ? 0ull : xa < 2 ? INW[24 + xa] : ((fw >> 32) ? ~0ull : 0ull);
+        const uint64_t Ti = Xi ^ Yi, Oi = Xi & Yi;
+        const uint32_t th = hiw ? hi32(Ti) : lo32(Ti), oh = hiw ? hi32(Oi) : lo32(Oi);
+        const uint32_t xh = hiw ? hi32(Xi) : lo32(Xi), yh = hiw ? hi32(Yi) : lo32(Yi);
+        // a_1: XOR rows (t, o) of limbs 2 half, 2 half + 1; CONST rows the word's four limbs
+        const uint32_t i0 = th & 0xffffu, i1 = e ? oh & 0xffffu : th >> 16;
+        const uint32_t i2 = e ? th >> 16 : hi32(Ti) & 0xffffu, i3 = e ? oh >> 16 : hi32(Ti) >> 16;
+        const uint32_t me = e ? ~0u : 0u, kb = 1u << S_CONST;
+        const uint64_t qrow = c.row0 - HPRE + 4ull * e;
+        uint32_t* const q = S + 4 * ((int)e - 7);  // rows -28 ..
+        auto put = [&](int col, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3) {
+          emit_at<MODE>(q + col * HSTR, col, qrow, v0, v1, v2, v3, inj);
+        };
+        put(A0, tag_of(i0), tag_of(i1), tag_of(i2), tag_of(i3));
+        put(A1, i0, i1, i2, i3);
+        put(A2, spread16(i0), spread16(i1), spread16(i2), spread16(i3));
+        put(A3, spread16(xh & 0xffffu) & me, 0u, spread16(xh >> 16) & me, 0u);
+        put(A4, spread16(yh & 0xffffu) & me, 0u, spread16(yh >> 16) & me, 0u);
+        put(A5, 0u, 0u, 0u, 0u);
+        put(A6, 0u, 0u, 0u, 0u);
+        put(A7, 0u, 0u, 0u, 0u);
+        put(A8, 0u, 0u, 0u, 0u);
+        put(A9, 0u, 0u, 0u, 0u);
+        if (e)
+          put(FXC, hiw ? 0u : 1u << S_XOR, 0u, 0u, 0u);
+        else
+          put(FXC, kb | (i0 << 16), kb | (i1 << 16), kb | (i2 << 16), kb | (i3 << 16));
+      }
       tick(2);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's staging is complete
       __builtin_amdgcn_wave_barrier();
@@ -1374,12 +1417,13 @@ fused_hr_kernel(const b2f_input* __restrict__ in, uint32_t n, const uint64_t* __
       // Line ownership: a 208-row tile is 832 bytes per column, so tile boundaries fall inside
       // 128-byte lines, and a line written half by one wave and half by another was measured
       // 15-25 % slower to store (tools/store_probe.hip, profiles/r03i_store_probe_align.jsonl).
-      // Each tile but an instance's first therefore also stores the previous tile's last kc
-      // quads (the head of the line its first row sits in, kc = 0..7 per column, rows -4 kc ..), and
-      // each tile but an instance's last leaves its last tc quads (the head of the line the next
-      // tile starts in) to the next tile: every line inside the instance's half-rounds is
-      // written by one store instruction of one wave.
-      const bool own_head = c.hr != 0, own_tail = c.hr + 1 == 2 * c.rounds;
+      // Each tile therefore also stores the last kc quads in front of it (the head of the line
+      // its first row sits in, kc = 0..7 per column, rows -4 kc ..: the previous tile's, or the
+      // init region's for an instance's first tile), and each tile leaves its last tc quads (the
+      // head of the line the next tile starts in) to what follows -- the next tile, or after an
+      // instance's last tile the boundary edge tile, which recomputes them from the last
+      // half-round's G 3 chain: every line of the trace is written by one store instruction of
+      // one wave.
       const uint32_t r4 = 4u * (uint32_t)c.row0, tr4 = 4u * (uint32_t)total_rows;
       const uint32_t adv_lo = (uint32_t)reinterpret_cast<uintptr_t>(adv) + r4;
       const uint32_t fix_lo = (uint32_t)reinterpret_cast<uintptr_t>(fixed) + r4;
@@ -1387,8 +1431,8 @@ fused_hr_kernel(const b2f_input* __restrict__ in, uint32_t n, const uint64_t* __
         uint32_t* base = (col < 10 ? adv + (uint64_t)col * total_rows : fixed) + c.row0;
         // the line offset needs only the address's low bits
         const uint32_t ba = col < 10 ? adv_lo + (uint32_t)col * tr4 : fix_lo;
-        const uint32_t kc = own_head ? (ba >> 4) & 7u : 0u;
-        const uint32_t tc = own_tail ? 0u : ((ba + 16u * HR_Q) >> 4) & 7u;
+        const uint32_t kc = (ba >> 4) & 7u;
+        const uint32_t tc = ((ba + 16u * HR_Q) >> 4) & 7u;
         const int32_t sq = (int32_t)lane - (int32_t)kc;  // the staged quad this lane stores
         const uint32_t* src = S + col * HSTR + 4 * sq;  // sq < 0: the rows in front
         const uint4 v = *reinterpret_cast<const uint4*>(src);
@@ -1503,12 +1547,21 @@ fused_hr_kernel(const b2f_input* __restrict__ in, uint32_t n, const uint64_t* __
 }
 
 // ============================================================================================
-// The edge launch (fused_edge_kernel): ONE wave tile per instance holds both of its edge
-// regions -- the init region on lanes 0-40 (INW h / m / t, FMASK, CONST IV, XOR v12..v14) and the
-// final region on lanes 41-56 (XOR3 + digest), so the init region's h cells (the XOR3 H operands'
-// copy sources) are staged in the same tile; lanes 57-60 recompute the final state from the last
-// half-round (the XOR3 V / U operands' producer values). The zero rows past the last instance
-// follow as 64-quad tiles. Fast 32-bit checks as in the half-round launch; a flagged tile is done
+// The edge launch (fused_edge_kernel): ONE wave tile per instance BOUNDARY b = 0 .. n holds the
+// two edge regions that are adjacent in memory -- the final region of instance b - 1 on lanes
+// 41-56 (XOR3 + digest; lanes 57-60 recompute that instance's final state from its last
+// half-round, the XOR3 V / U operands' producer values) and the init region of instance b on
+// lanes 0-40 (INW h / m / t, FMASK, CONST IV, XOR v12..v14) -- and stores them as one contiguous
+// run per column, so the 128-byte line the two regions share is written once, by one store
+// instruction (boundary 0 has the init region only, boundary n the final region only). The run
+// begins and ends on a line: in front it takes the last tc quads of instance b - 1's last
+// half-round tile (recomputed by lanes 57-63 from that half-round's G 3 chain, which producer
+// lane 3 forms anyway), and it leaves the init region's last kc quads to instance b's first
+// half-round tile (whose tail lanes form them): tc and kc are the line offsets, in quads, of the
+// final region's first row and of the first tile's first row in that column.
+// The XOR3 H operands' copy sources are the init h cells of instance b - 1, another tile's: the
+// check takes them from the spread limbs of in[b - 1].h (the limb table's last 32 entries), which
+// is what that tile staged. The zero rows past the last instance follow as 64-quad tiles. Fast 32-bit checks as in the half-round launch; a flagged tile is done
 // again, region by region, by the exact edge path (edge_tile: assignment, stores, exact checks).
 namespace edge2 {
 constexpr uint32_t NQ_I = INIT_Q, NQ_F = FINAL_Q, NQ = INIT_Q + FINAL_Q;  // 41, 16, 57
@@ -1563,7 +1616,9 @@ __constant__ EdgeProgs c_eprogs = make_edge_progs();
 // Copy checks of an edge tile (120): the init XORs' operands (IV_4..6 from the CONST blocks, t0 /
 // t1 / fmask from their INW / FMASK blocks) and the XOR3 operands (H from the INW h blocks, V and
 // U from the final state's producer values). Entry: dst row (bits 0-7), dst column a_3 + c
-// (8-9), source kind (10: 0 staged a_2 cell at row bits 11-18, 1 limb-table entry bits 11-16).
+// (8-9), source kind (10: 0 staged a_2 cell at row bits 11-18, 1 limb-table entry bits 11-16),
+// bit 19: an XOR3 H operand, whose staged source is the init region of the final region's own
+// instance (a boundary tile holds another instance's: it reads limb-table entry 64 + the row).
 constexpr int E_CHECKS = 120;
 struct EdgeChecks {
   uint32_t e[128];
@@ -1580,7 +1635,7 @@ constexpr EdgeChecks make_edge_checks() {
   for (uint32_t i = 0; i < 8; i++)
     for (uint32_t k = 0; k < 4; k++) {
       const uint32_t row = INIT_ROWS + 8 * i + 2 * k;
-      T.e[n++] = row | (0u << 8) | ((4 * i + k) << 11);
+      T.e[n++] = row | (0u << 8) | ((4 * i + k) << 11) | (1u << 19);
       T.e[n++] = row | (1u << 8) | (1u << 10) | ((4 * i + k) << 11);
       T.e[n++] = row | (2u << 8) | (1u << 10) | ((4 * (i + 8) + k) << 11);
     }
@@ -1591,30 +1646,35 @@ constexpr EdgeChecks make_edge_checks() {
 static_assert(make_edge_checks().e[0] != 0xffffffffu, "120 edge copy checks");
 __constant__ EdgeChecks c_echecks = make_edge_checks();
 
-// wave LDS (words): staging [11][STR_E], limb table (spread limbs of the final state, 4 w + k),
-// producer outputs (16 u64 by word). The exact edge path (edge_tile, in edge_redo_kernel) reuses the same words with
+// wave LDS (words): staging [11][STR_E], limb table (spread limbs of the final state, 4 w + k,
+// then of the final region's h words, 64 + 4 i + k), producer outputs (16 u64 by word), the
+// last half-round's G 3 chain record (14 u64). The exact edge path (edge_tile, in edge_redo_kernel) reuses the same words with
 // its own carve (staging [11][208], prod, canonical flags), inside this one.
 constexpr int E_LT = NSTAGE * STR_E;
-constexpr int E_PROD = E_LT + 64;
-constexpr int EW_WORDS = E_PROD + 32;
+constexpr int E_PROD = E_LT + 96;
+constexpr int E_GP = E_PROD + 32;  // the chain record of the final side's last half-round G 3 (14 u64)
+constexpr int EW_WORDS = E_GP + 32;
 static_assert(EW_WORDS >= WAVE_WORDS, "the exact edge path's carve fits");
 static_assert(EW_WORDS <= hr2::HW_WORDS, "the half-round launch's wave region holds an edge tile");
 constexpr int E_ACC = 0, E_IV = 24, E_SG = E_IV + 16, E_WAVE = E_SG + 40;
 constexpr int E_WORDS = E_WAVE + WAVES * EW_WORDS;
-static_assert(E_WAVE % 4 == 0 && EW_WORDS % 4 == 0 && E_PROD % 2 == 0, "aligned carve");
+static_assert(E_WAVE % 4 == 0 && EW_WORDS % 4 == 0 && E_PROD % 2 == 0 && E_GP % 4 == 0, "aligned carve");
 static_assert(4 * E_WORDS < 65536, "LDS byte addresses fit 16 bits");
 
-// store of one region of an edge tile: lane `lane` writes quad lane - q0 of the region
-__device__ __forceinline__ void region_store(uint32_t* base, uint32_t nq, uint32_t lane, uint32_t q0, uint4 v) {
+// store of an edge tile's run of nq quads: the lane writes quad q of it (Q_NONE: no quad)
+constexpr uint32_t Q_NONE = 0x00ffffffu;  // + a few quads still past every range, no wrap
+__device__ __forceinline__ void region_store(uint32_t* base, uint32_t nq, uint32_t q, uint4 v) {
   const uint64_t a = reinterpret_cast<uint64_t>(base);
   const i32x4 rsrc = {(int32_t)(uint32_t)a, (int32_t)(uint32_t)(a >> 32), (int32_t)(nq * 16u), 0x00020000};
   b2f_raw_buffer_store_v4(i32x4{(int32_t)v.x, (int32_t)v.y, (int32_t)v.z, (int32_t)v.w}, rsrc,
-                          (int)(16u * (lane - q0)), 0, EDGE_NT);  // lanes outside: past the range
+                          (int)(16u * q), 0, EDGE_NT);  // Q_NONE: past the range
 }
 
-struct ECtx {
-  uint32_t inst, rounds;
-  uint64_t off, st;
+struct ECtx {  // boundary b: the init side is instance b, the final side instance b - 1
+  uint32_t inst, rounds;     // the init region's instance (b, or n - 1 at b = n: staged, not stored)
+  uint64_t off;
+  uint32_t finst, frounds;   // the final region's (b - 1, or 0 at b = 0: staged, not stored)
+  uint64_t foff, fst;
 };
 }  // namespace edge2
 
@@ -1637,7 +1697,8 @@ __device__ __forceinline__ void stage_e(uint32_t* S, int col, uint32_t lane, uin
 
 
 // Per-lane constants of an edge tile (lane = quad of the init region 0-40 / final region 41-56;
-// lanes >= 57 check a repeat of quads 0-6).
+// lanes >= 57 check a repeat of quads 0-6). BND: a boundary tile (the fused path), whose XOR3 H
+// copy sources are limb-table entries; the eval's tile holds one instance's two regions.
 struct ELane {
   uint32_t selL[4], selH[4];
   uint32_t kind, qq, a;
@@ -1646,6 +1707,7 @@ struct ELane {
   uint32_t aQ, aQn;   // the quad's and the next quad's staged rows (column a_0)
   uint32_t ce[2];     // copy checks (dst | src << 16)
 };
+template <bool BND = false>
 __device__ __forceinline__ ELane make_elane(uint32_t lane, uint32_t Sb, const uint64_t* IV) {
   using namespace edge2;
   ELane E;
@@ -1684,7 +1746,9 @@ __device__ __forceinline__ ELane make_elane(uint32_t lane, uint32_t Sb, const ui
   for (int it = 0; it < 2; it++) {
     const uint32_t e = c_echecks.e[it * FW + lane];
     const uint32_t dst = Sb + 4 * ((A3 + ((e >> 8) & 3u)) * STR_E + (e & 255u));
-    const uint32_t src = (e >> 10) & 1u ? Sb + 4 * (E_LT + ((e >> 11) & 63u)) : Sb + 4 * (A2 * STR_E + ((e >> 11) & 255u));
+    const uint32_t src = (e >> 10) & 1u           ? Sb + 4 * (E_LT + ((e >> 11) & 63u))
+                         : BND && ((e >> 19) & 1u) ? Sb + 4 * (E_LT + 64 + ((e >> 11) & 31u))
+                                                   : Sb + 4 * (A2 * STR_E + ((e >> 11) & 255u));
     E.ce[it] = dst | (src << 16);
   }
   return E;
@@ -1731,8 +1795,8 @@ __device__ __forceinline__ uint32_t edge_fast_checks(const ELane& E) {
   return acc;
 }
 
-// The edge tiles t_first, t_first + W, ... of a batch (one per instance, then the zero rows past
-// the last instance) on this wave, staged in the wave region S (EW_WORDS words): the body of the
+// The edge tiles t_first, t_first + W, ... of a batch (one per instance boundary 0 .. n, then the
+// zero rows past the last instance) on this wave, staged in the wave region S (EW_WORDS words): the body of the
 // edge launch, and the last phase of the half-round launch (each wave walks edge tiles once its
 // instances and listed segments are done, so the edge work fills the half-round launch's tail
 // instead of waiting for it).
@@ -1750,17 +1814,38 @@ __device__ __forceinline__ void edge_walk(uint32_t* S, uint32_t lane, uint64_t t
   const uint32_t Sb = lds_byte(S);
   uint64_t* prod = reinterpret_cast<uint64_t*>(S + E_PROD);
   // per-lane constants
-  const ELane E = make_elane(lane, Sb, IV);
+  const ELane E = make_elane<true>(lane, Sb, IV);
   const uint32_t kind = E.kind, qq = E.qq, wa = E.a;
   const uint32_t mFM = E.mFM, mX3 = E.mX3, mXOR = E.mXOR, m78 = E.m78;
   const uint4 fxq = E.fxq;
   const bool plane = lane >= NQ && lane < NQ + 4;
+  const bool flane = lane >= NQ_I;  // the final side: its region's and the producer lanes
   const uint32_t pg = lane - NQ;
+  // The tail lanes (57-63, after their producer work): quads 45-51 of the final side's last
+  // half-round tile, i.e. quads 6-12 of its G 3, formed as the half-round launch's tail lanes
+  // form them, from that G's chain record (E_GP: a d c b a1 d1 c1 b1 a2 d2 c2 mx my 0; producer
+  // lane 3 has the whole chain). That tile left the last tc of them, the head of the line the
+  // final region starts in, to this tile's store.
+  const bool tlane = lane >= NQ;
+  const QuadProg& TQ = c_qprogs.q[tlane ? G_QUADS - 7 + pg : 0u];
+  uint32_t tselL[4], tselH[4], tslot[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    tselL[j] = TQ.selL[j];
+    tselH[j] = TQ.selH[j];
+    tslot[j] = TQ.slot[j];
+  }
+  const uint32_t tslA = TQ.slA, tslB = TQ.slB, tfx0 = TQ.fx0, tfl = TQ.flags;
+  const uint32_t tmadd = (tfl & 1u) ? ~0u : 0u, tmzm = (tfl & 2u) ? 0x7fff7fffu : ~0u, tm63 = (tfl & 2u) ? ~0u : 0u;
+  const uint32_t tmhw = (tfl & 4u) ? ~0u : 0u, trsh = (tfl & 2u) ? 31u : 24u;
+  const uint32_t tst = step_of_quad(tlane ? G_QUADS - 7 + pg : 0u);
+  const uint32_t aTX = Sb + 4 * E_GP + 8 * tst, aTM = Sb + 4 * E_GP + 8 * (tst == 0 ? 11u : tst == 4 ? 12u : 13u);
 
   {
     const uint64_t used_rows = off[n];
     const uint64_t n_pad = ((total_rows - used_rows) / 4 + PAD_Q - 1) / PAD_Q;
-    const uint64_t t_all = (uint64_t)n + n_pad;
+    const uint64_t n_b = n ? (uint64_t)n + 1 : 0;  // boundary tiles 0 .. n
+    const uint64_t t_all = n_b + n_pad;
     // edge tiles t, t + W, ... from t_first, or (ectr) claimed from the launch's counter: a wave
     // holds the tile it works on and the next two, whose context it loads ahead
     // (B2F_FUSED_EDGE_CHUNK consecutive tiles per claim)
@@ -1778,19 +1863,25 @@ __device__ __forceinline__ void edge_walk(uint32_t* S, uint32_t lane, uint64_t t
     };
     uint64_t t = ectr ? claim() : t_first;
     uint64_t t1 = ectr ? claim() : t + W;
+    // A side without a region (the final side of boundary 0, the init side of boundary n) takes
+    // its neighbour's instance: staged and checked like any other, never stored or flagged.
     auto ectx = [&](uint64_t tt) {
       ECtx c;
-      const uint32_t i = tt < n ? (uint32_t)tt : 0u;
+      const uint32_t b = tt < n_b ? (uint32_t)tt : 0u;
+      const uint32_t i = b < n ? b : (n ? n - 1 : 0u), f = b ? b - 1 : 0u;
       c.inst = i;
       c.off = off[i];
       c.rounds = in[i].rounds;
-      c.st = 2 * ((c.off - (uint64_t)FIXED_ROWS * i) / ROUND_ROWS) + i;
+      c.finst = f;
+      c.foff = off[f];
+      c.frounds = in[f].rounds;
+      c.fst = 2 * ((c.foff - (uint64_t)FIXED_ROWS * f) / ROUND_ROWS) + f;
       return c;
     };
     // the words of one tile: init lanes their block's word, final lanes h_i and the final state's
     // v_i, v_{i+8}; producer lanes the last half-round's G operands (or the initial words at 0 rounds)
     auto words = [&](const ECtx& c) {
-      const b2f_input* x = in + c.inst;
+      const b2f_input* x = in + (flane ? c.finst : c.inst);
       const uint64_t* fw = reinterpret_cast<const uint64_t*>(&x->rounds);  // rounds | f << 32
       const uint64_t* p[6] = {fw, fw, fw, fw, fw, fw};
       if (lane < 26) {
@@ -1800,18 +1891,18 @@ __device__ __forceinline__ void edge_walk(uint32_t* S, uint32_t lane, uint64_t t
         p[0] = a < 2 ? x->t + a : fw;
       } else if (lane >= NQ_I && lane < NQ) {
         const uint32_t i = (lane - NQ_I) >> 1;
-        const uint64_t* fin = rec + 16ull * (c.st + 2ull * c.rounds);
+        const uint64_t* fin = rec + 16ull * (c.fst + 2ull * c.frounds);
         p[0] = x->h + i;
         p[1] = fin + i;
         p[2] = fin + i + 8;
       } else if (plane) {
-        if (c.rounds == 0) {
+        if (c.frounds == 0) {
           p[0] = x->h + pg;
           p[1] = x->h + pg + 4;
           p[3] = pg < 2 ? x->t + pg : fw;
         } else {
-          const uint32_t hp = 2 * c.rounds - 1, g = pg + 4;  // the last half-round: diagonal G's
-          const uint64_t* s = rec + 16ull * (c.st + hp);
+          const uint32_t hp = 2 * c.frounds - 1, g = pg + 4;  // the last half-round: diagonal G's
+          const uint64_t* s = rec + 16ull * (c.fst + hp);
           const uint32_t gi = gidx_word(g);
           const uint8_t* sg = Sg + 16 * ((hp >> 1) % 10) + 2 * g;
           p[0] = s + (gi & 15u);
@@ -1836,10 +1927,14 @@ __device__ __forceinline__ void edge_walk(uint32_t* S, uint32_t lane, uint64_t t
       const uint64_t t2 = ectr ? claim() : t1 + W;
       const ECtx cnn = ectx(t2);  // scalar loads, two tiles ahead
       const Ops Pn = words(cn);         // unconditional: the compiler counts vmcnt exactly
-      if (t < n) {
-        // ---- one instance's init + final regions
-        const uint64_t row_i = c.off, row_f = c.off + INIT_ROWS + (uint64_t)ROUND_ROWS * c.rounds;
-        const uint64_t qrow = lane < NQ_I ? row_i + 4ull * lane : row_f + 4ull * (lane - NQ_I);
+      if (t < n_b) {
+        // ---- boundary t: the final region of instance t - 1 and the init region of instance t,
+        // adjacent in memory (row_f + 4 NQ_F is the next instance's first row)
+        const bool has_i = t < n, has_f = t != 0;
+        const uint64_t row_i = c.off, row_f = c.foff + INIT_ROWS + (uint64_t)ROUND_ROWS * c.frounds;
+        // a region this boundary does not have is at no row (the test hook never lands in it)
+        const uint64_t qrow = lane < NQ_I ? (has_i ? row_i + 4ull * lane : ~0ull)
+                                          : (has_f ? row_f + 4ull * (lane - NQ_I) : ~0ull);
         const uint64_t w0 = P.w[0];
         const bool fbit = (w0 >> 32) != 0;
         uint64_t X = 0, Y = 0, U = 0, T, O = 0;
@@ -1882,7 +1977,18 @@ __device__ __forceinline__ void edge_walk(uint32_t* S, uint32_t lane, uint64_t t
           stage_e<MODE>(S, A9, lane, qrow, 0u, 0u, 0u, 0u, inj);
           stage_e<MODE>(S, FXC, lane, qrow, fxq.x, fxq.y, fxq.z, fxq.w, inj);
         }
-        if (plane) producer_words(prod, P, pg, c.rounds == 0, 2 * c.rounds - 1, IV);
+        if (plane) producer_words(prod, P, pg, c.frounds == 0, 2 * c.frounds - 1, IV);
+        if (pg == 3 && c.frounds != 0) {  // the last half-round's G 3 chain, for the tail lanes
+          const uint64_t ga = P.w[0], gb = P.w[1], gc = P.w[2], gd = P.w[3], mx = P.w[4], my = P.w[5];
+          const uint64_t a1 = ga + gb + mx, d1 = rotr64(gd ^ a1, 32), c1 = gc + d1, b1 = rotr64(gb ^ c1, 24);
+          const uint64_t a2 = a1 + b1 + my, d2 = rotr64(d1 ^ a2, 16), c2 = c1 + d2;
+          uint64_t* gp = reinterpret_cast<uint64_t*>(S + E_GP);
+          gp[0] = ga, gp[1] = gd, gp[2] = gc, gp[3] = gb, gp[4] = a1, gp[5] = d1, gp[6] = c1;
+          gp[7] = b1, gp[8] = a2, gp[9] = d2, gp[10] = c2, gp[11] = mx, gp[12] = my, gp[13] = 0;
+        }
+        // limb table, second part: the spread limbs of the final region's h words (the XOR3 H
+        // operands' copy sources: what the init region of that instance stages as a_2)
+        if (flane && lane < NQ) *reinterpret_cast<uint2*>(S + E_LT + 64 + 4 * wa + 2 * qq) = make_uint2(sx0, sx1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         {  // limb table: spread limb (lane & 3) of final state word lane >> 2
@@ -1891,33 +1997,107 @@ __device__ __forceinline__ void edge_walk(uint32_t* S, uint32_t lane, uint64_t t
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
-        // ---- stores: the init region (lanes 0-40) and the final region (lanes 41-56)
+        // ---- store: one run per column -- the last tc quads of the final side's last half-round
+        // tile (tail lanes), its final region (lanes 41-56), then the init region (lanes 0-40)
+        // less its last kc quads: the run begins and ends on a 128-byte line
         if (MODE & FZ_STORE) {
           const uint32_t l = lane < NQ ? lane : 0;
+          const uint64_t row_s = has_f ? row_f : row_i;
+          const uint32_t nf = has_f ? NQ_F : 0u, nqs = nf + (has_i ? NQ_I : 0u);
+          const uint32_t sq = lane < NQ_I ? (has_i ? lane + nf : Q_NONE) : (has_f && lane < NQ ? lane - NQ_I : Q_NONE);
+          // the init region's last kc quads of a column (the head of the line the instance's
+          // first half-round tile starts in) are that tile's: store_col's kc at hr = 0
+          const bool hr_head = has_i && c.rounds != 0;
+          const uint32_t r4 = 4u * (uint32_t)(row_i + INIT_ROWS), tr4 = 4u * (uint32_t)total_rows;
+          const uint32_t adv_lo = (uint32_t)reinterpret_cast<uintptr_t>(adv) + r4;
+          const uint32_t fix_lo = (uint32_t)reinterpret_cast<uintptr_t>(fixed) + r4;
+          // the quads in front of the final region up to its line's head (store_col's tc at the
+          // last half-round tile), formed here: the cells of hr2's tile loop, step 4
+          const bool hr_tail = has_f && c.frounds != 0;
+          const uint32_t f4 = 4u * (uint32_t)row_f;
+          const uint32_t advf_lo = (uint32_t)reinterpret_cast<uintptr_t>(adv) + f4;
+          const uint32_t fixf_lo = (uint32_t)reinterpret_cast<uintptr_t>(fixed) + f4;
+          const uint64_t tX = ld64(aTX), tY = ld64(aTX + 24), tM = ld64(aTM);
+          const uint64_t ts1 = tX + tY, tSm = ts1 + tM, tZ = tX ^ tY, tO = tX & tY;
+          const uint32_t tcy = ((uint32_t)(ts1 < tX) + (uint32_t)(tSm < ts1)) & tmadd;
+          const uint32_t Tl = sel32(tmadd, lo32(tSm), lo32(tZ) & tmzm), Th = sel32(tmadd, hi32(tSm), hi32(tZ) & tmzm);
+          const uint32_t zu = sel32(tm63, lo32(tZ), hi32(tZ)), zv = sel32(tm63, hi32(tZ), lo32(tZ));
+          const uint32_t Wl = __builtin_amdgcn_alignbit(zu, zv, trsh), Wh = __builtin_amdgcn_alignbit(zv, zu, trsh);
+          uint32_t tv[4];
+#pragma unroll
+          for (int j = 0; j < 4; j++) tv[j] = perm(lo32(tO), Tl, tselL[j]) | perm(hi32(tO), Th, tselH[j]);
+          const uint32_t xA = perm(hi32(tX), lo32(tX), tslA), xB = perm(hi32(tX), lo32(tX), tslB);
+          const uint32_t yA = perm(hi32(tY), lo32(tY), tslA), yB = perm(hi32(tY), lo32(tY), tslB);
+          const uint32_t wA = perm(Wh, Wl, tslA) & tmhw, wB = perm(Wh, Wl, tslB) & tmhw;
+          const uint32_t zA = (perm(hi32(tZ), lo32(tZ), tslA) >> 15) & tm63;
+          const uint32_t zB = (perm(hi32(tZ), lo32(tZ), tslB) >> 15) & tm63;
+          const uint32_t P3 = sel32(tmadd, hi32(tX), spread16(xB)), Q3 = sel32(tmadd, lo32(tX), spread16(xA));
+          const uint32_t P4 = sel32(tmadd, hi32(tY), spread16(yB)), Q4 = sel32(tmadd, lo32(tY), spread16(yA));
+          const uint32_t swA = spread16(wA), swB = spread16(wB);
+          auto slots = [&](uint32_t hi, uint32_t lo) {
+            return make_uint4(perm(hi, lo, tslot[0]), perm(hi, lo, tslot[1]), perm(hi, lo, tslot[2]), perm(hi, lo, tslot[3]));
+          };
+          const uint64_t trow = row_f - HPRE + 4ull * pg;  // the tail lane's quad (no row if !hr_tail)
+          auto tail_cells = [&](int col) {
+            uint4 v = col == A0   ? make_uint4(tag_of(tv[0]), tag_of(tv[1]), tag_of(tv[2]), tag_of(tv[3]))
+                      : col == A1 ? make_uint4(tv[0], tv[1], tv[2], tv[3])
+                      : col == A2 ? make_uint4(spread16(tv[0]), spread16(tv[1]), spread16(tv[2]), spread16(tv[3]))
+                      : col == A3 ? slots(P3, Q3)
+                      : col == A4 ? slots(P4, Q4)
+                      : col == A5 ? make_uint4(perm(hi32(tM), lo32(tM), limb_sel(0)), perm(hi32(tM), lo32(tM), limb_sel(1)),
+                                               perm(hi32(tM), lo32(tM), limb_sel(2)), perm(hi32(tM), lo32(tM), limb_sel(3)))
+                      : col == A6 ? slots(zB, zA)
+                      : col == A7 ? slots(wB, wA)
+                      : col == A8 ? slots(swB, swA)
+                      : col == A9 ? make_uint4(tcy, 0u, 0u, 0u)
+                                  : make_uint4(tfx0, 0u, 0u, 0u);
+            if (MODE & FZ_INJECT) {
+              if (hr_tail && (inj.row >> 2) == (trow >> 2) && inj.col == (uint32_t)col) {
+                const uint32_t j = (uint32_t)inj.row & 3u;
+                v.x ^= j == 0 ? inj.mask : 0u;
+                v.y ^= j == 1 ? inj.mask : 0u;
+                v.z ^= j == 2 ? inj.mask : 0u;
+                v.w ^= j == 3 ? inj.mask : 0u;
+              }
+            }
+            return v;
+          };
 #pragma unroll
           for (int col = 0; col < NSTAGE; col++) {
-            const uint4 cv = *reinterpret_cast<const uint4*>(S + col * STR_E + 4 * l);
+            const uint4 sv = *reinterpret_cast<const uint4*>(S + col * STR_E + 4 * l);
+            const uint4 tq = tail_cells(col);
+            const uint4 cv = tlane ? tq : sv;
             uint32_t* base = col < 10 ? adv + (uint64_t)col * total_rows : fixed;
-            region_store(base + row_i, NQ_I, lane, 0, cv);
-            region_store(base + row_f, NQ_F, lane, NQ_I, cv);
+            const uint32_t ba = col < 10 ? adv_lo + (uint32_t)col * tr4 : fix_lo;
+            const uint32_t kc = hr_head ? (ba >> 4) & 7u : 0u;
+            const uint32_t bf = col < 10 ? advf_lo + (uint32_t)col * tr4 : fixf_lo;
+            const uint32_t tc = hr_tail ? (bf >> 4) & 7u : 0u;
+            // tail lane k holds quad 45 + k: the last tc of the seven go out, in front of the rest
+            const uint32_t sqc = tlane ? (pg + tc >= 7u ? pg + tc - 7u : Q_NONE) : sq + tc;
+            region_store(base + row_s - 4 * tc, nqs - kc + tc, sqc, cv);
           }
         }
         asm volatile("" ::"v"(Pn.w[0]), "v"(Pn.w[1]), "v"(Pn.w[2]), "v"(Pn.w[3]), "v"(Pn.w[4]), "v"(Pn.w[5]));
         // ---- fast checks
         const uint32_t acc = edge_fast_checks<MODE>(E);
-        bool bad = acc != 0;
-        if (MODE & FZ_INJECT)  // the test hook: its instance is checked exactly
-          bad |= inj.row >= c.off && inj.row < c.off + FIXED_ROWS + (uint64_t)ROUND_ROWS * c.rounds;
-        // rare: the instance goes to the redo list (edge_redo_kernel: the exact edge path,
-        // exact bookkeeping); a list slot per instance, so it cannot overflow
-        if (__builtin_amdgcn_ballot_w64(bad) && lane == 0) {
-          const uint32_t slot = atomicAdd(redo, 1u);
-          redo[1 + slot] = c.inst;
+        const bool bad = __builtin_amdgcn_ballot_w64(acc != 0) != 0;
+        bool bad_i = has_i && bad, bad_f = has_f && bad;
+        if (MODE & FZ_INJECT) {  // the test hook: its instance is checked exactly
+          bad_i |= has_i && inj.row >= c.off && inj.row < c.off + FIXED_ROWS + (uint64_t)ROUND_ROWS * c.rounds;
+          bad_f |= has_f && inj.row >= c.foff && inj.row < c.foff + FIXED_ROWS + (uint64_t)ROUND_ROWS * c.frounds;
+        }
+        // rare: the regions go to the redo list (edge_redo_kernel: the exact edge path, exact
+        // bookkeeping), as 2 instance + (0 init, 1 final). A region belongs to one boundary tile,
+        // so it is listed at most once: two slots per instance, the list cannot overflow.
+        if ((bad_i || bad_f) && lane == 0) {
+          const uint32_t slot = atomicAdd(redo, (uint32_t)bad_i + (uint32_t)bad_f);
+          if (bad_i) redo[1 + slot] = 2 * c.inst;
+          if (bad_f) redo[1 + slot + (uint32_t)bad_i] = 2 * c.finst + 1;
         }
       } else {
         // ---- the zero rows past the last instance: written and checked from registers (a
         // selector here can only come from the test hook, and its gate is deferred)
-        const uint64_t row0 = used_rows + (uint64_t)PAD_Q * 4 * (t - n);
+        const uint64_t row0 = used_rows + (uint64_t)PAD_Q * 4 * (t - n_b);
         const uint64_t left = row0 < total_rows ? (total_rows - row0) >> 2 : 0;
         const uint32_t nq = (uint32_t)(left < PAD_Q ? left : PAD_Q);
         const uint64_t qrow = row0 + 4ull * lane;
@@ -2000,8 +2180,10 @@ fused_edge_kernel(const b2f_input* __restrict__ in, uint32_t n, const uint64_t* 
   flush_report(A, rep, tid);
 }
 
-// The edge regions of the instances the edge launch flagged, done again by the exact edge
-// path (assignment and stores repeated with the same values, every check recorded exactly).
+// The edge regions the edge tiles flagged (list entries 2 instance + region), each done again
+// once by the exact edge path (assignment and stores repeated with the same values, every check
+// recorded exactly). An instance's two regions are flagged by two boundary tiles, each for its
+// own region, so no region -- and no counter -- is taken twice.
 template <int MODE>
 __global__ void __launch_bounds__(FW * WAVES)
 edge_redo_kernel(const b2f_input* __restrict__ in, const uint64_t* __restrict__ off,
@@ -2023,9 +2205,10 @@ edge_redo_kernel(const b2f_input* __restrict__ in, const uint64_t* __restrict__ 
   if (*status == 0) {
     const uint32_t cnt = redo[0];
     for (uint32_t k = blockIdx.x * WAVES + wv; k < cnt; k += gridDim.x * WAVES) {
-      const uint32_t i = __builtin_amdgcn_readfirstlane(redo[1 + k]);
-#pragma unroll 1
-      for (int part = 0; part < 2; part++) {
+      const uint32_t e = __builtin_amdgcn_readfirstlane(redo[1 + k]);
+      const uint32_t i = e >> 1;
+      {
+        const int part = (int)(e & 1u);
         Ctx c;
         c.inst = i;
         c.rounds = in[i].rounds;
@@ -2434,7 +2617,8 @@ namespace b2f {
 
 // Scratch of the fused path: tile descriptors for `tiles` instance tiles (written and read by the
 // eval's fast pass only) and the deferred row list (count + DEFER_CAP rows).
-// + the edge launch's redo list (count + one slot per instance; tiles >= instances)
+// + the edge launch's redo list (count + one slot per edge region, two per instance; tiles >=
+//   2 instances: fused_instance_tiles)
 // + 16 bytes: the eval's band counter and dirty word (each with a spare word after it)
 // + 8 bytes: the fused half-round launch's instance counter and edge-tile counter
 // Every part has its own words: no call reads a word that only another kind of call writes.
@@ -2555,9 +2739,9 @@ hipError_t launch_fill_eval(const b2f_input* d_in, uint32_t n, const uint64_t* d
       nb = 2;
     per_cu[1] = nb;
   }
-  // the edge tiles (one per instance) plus the zero rows; no more workgroups than they fill
-  // (the zero-row count here is an upper bound)
-  const uint64_t edge_tiles = (uint64_t)n + ((total_rows / 4) + PAD_Q - 1) / PAD_Q;
+  // the edge tiles (one per instance boundary) plus the zero rows; no more workgroups than they
+  // fill (the zero-row count here is an upper bound)
+  const uint64_t edge_tiles = (uint64_t)n + 1 + ((total_rows / 4) + PAD_Q - 1) / PAD_Q;
   const uint64_t edge_wgs = (edge_tiles + WAVES - 1) / WAVES;
   // Fewer half-round workgroups than fit: 3 per CU (12 waves) write the trace faster than 2 or 4
   // per CU (same-process A/B 11.48 vs 12.89 / 12.91 ms, profiles/r03o_ab_percu.txt): enough
