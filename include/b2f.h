@@ -56,7 +56,8 @@ extern "C" {
 #define B2F_ERR_INPUT 6     /* malformed EIP-152 input (length != 213 or f not 0/1) */
 #define B2F_ERR_FIELD 7     /* (at b2f_sync) a grand product's denominator product is zero: a
                                challenge collides with a cell value, its z column is meaningless;
-                               or an NTT's omega is not a primitive 2^k-th root of unity */
+                               or an NTT's or a quotient call's omega is not a primitive
+                               root of unity of its domain; or the vanishing divide met X^n = 1 */
 #define B2F_ERR_CHECK 8     /* (at b2f_sync) an internal cross-check failed -- a library defect:
                                the lookup's permuted columns do not multiply to the product of
                                its input columns (its columns are wrong), or the fused pass's
@@ -190,7 +191,8 @@ B2F_API uint64_t b2f_copy_constraints(uint32_t rounds, uint32_t* out4, uint64_t 
 
 /* Wait for `stream` and return the first device-side error of the calls issued since the
  * previous b2f_sync (B2F_ERR_LAYOUT / B2F_ERR_ROUNDS from fill/eval, B2F_ERR_FIELD from the
- * lookup / permutation grand products and the NTT's root check), then clear it. */
+ * lookup / permutation grand products, the root checks of the NTT and the quotient calls and the
+ * vanishing divide), then clear it. */
 B2F_API int b2f_sync(b2f_ctx* ctx, void* stream);
 
 /* Host-pointer conveniences (allocate, copy, run, copy back; blocking). b2f_fill sizes the
@@ -387,6 +389,78 @@ B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_
                                 uint32_t direction, uint32_t form, uint64_t* d_out,
                                 uint64_t out_rows, void* stream);
 
+/* The permutation and lookup terms of the quotient numerator on the extended coset, and the
+ * division by the vanishing polynomial (halo2_proofs 0.3.0 plonk/permutation/prover.rs and
+ * plonk/lookup/prover.rs Committed::construct, EvaluationDomain::divide_by_vanishing_poly). The
+ * custom-gate terms are not here: the term calls fold into a caller-supplied accumulator in
+ * halo2's order (gates, then the permutation, then each lookup), so a gate pass composes with them.
+ * Shared conventions: columns are d[(c * rows + i) * 4 + limb] in `form` (any B2F_FP_*; the
+ * canonical forms convert at load and store, inputs reduced); n = 2^k, n_ext = 2^ext_k,
+ * 1 <= k < ext_k <= 28, rot = 2^(ext_k - k); extended row i is the point X_i = shift omega_ext^i
+ * and a rotation by r circuit rows reads extended row (i + r rot) mod n_ext; usable_rows =
+ * 2^k - blinding_factors - 1 as in the column calls; omega_ext, shift, delta and the challenges
+ * are canonical elements of the field of `form`. The fold: h = h_in (zero when d_h_in is NULL),
+ * then h = h y + e_t for each term in order, i.e. h_out = y^T h_in + sum_t y^(T-1-t) e_t. d_h_in
+ * == d_h_out is allowed (a row reads only its own h); any other overlap of h_out with h_in or
+ * with an input block is B2F_ERR_ARG. Common errors, nothing launched on either: B2F_ERR_ARG for a
+ * null or misaligned (16 B) pointer, k or ext_k out of range, form > 3, an element >= p, shift ==
+ * 0; B2F_ERR_ROWS for usable_rows >= 2^k, rows < n_ext, out_rows < 2^k. Asynchronous on `stream`;
+ * each call is one B2F_KERNEL_QUOTIENT region.
+ *
+ * b2f_lagrange_selectors_dev (keygen data): three Lagrange-form columns over 2^k rows at
+ * d_out[(c * out_rows + i) * 4 + limb]: c = 0 l_0 (1 at row 0), 1 l_last (1 at row usable_rows),
+ * 2 l_active = 1 - l_last - l_blind (1 on rows < usable_rows), zero elsewhere; rows >= 2^k are
+ * not touched. Two b2f_ntt_columns_dev calls take them to the coset like any other column. */
+B2F_API int b2f_lagrange_selectors_dev(b2f_ctx* ctx, uint32_t k, uint64_t usable_rows, uint32_t form,
+                                       uint64_t* d_out, uint64_t out_rows, void* stream);
+
+/* Permutation terms. All blocks are on the extended coset with stride rows >= n_ext: d_l the
+ * three selector columns; d_advice the ten advice columns in halo2 order, the block
+ * b2f_export_fp_dev writes (v_j = column b2f_halo2_column_index(j + 1), j < 8; the two columns
+ * outside the permutation are not read); d_sigma the eight sigma columns; d_z the sets =
+ * ceil(8 / chunk_len) grand-product columns (1 <= chunk_len <= 8). Terms per row, T = 2 sets + 1:
+ *   l_0 (1 - z_0)
+ *   l_last (z_last^2 - z_last),                  z_last = set sets - 1
+ *   l_0 (z_s - z_{s-1}(w^usable_rows X)),        s = 1 .. sets - 1
+ *   l_active (z_s(w X) prod_{j in s} (v_j + beta sigma_j + gamma)
+ *             - z_s prod_{j in s} (v_j + beta delta^j X_i + gamma)),   s = 0 .. sets - 1
+ * (j runs over all eight columns across the sets; the last set may be short). X_i comes from a
+ * two-level power table built on the device once per (field, ext_k, omega_ext, shift) and cached
+ * in the context (4 domains, replaced round-robin). B2F_ERR_FIELD at b2f_sync when
+ * omega_ext^(n_ext / 2) != -1. */
+B2F_API int b2f_quotient_permutation_dev(b2f_ctx* ctx, uint32_t k, uint32_t ext_k, uint64_t usable_rows,
+                                         const uint64_t* d_l, const uint64_t* d_advice,
+                                         const uint64_t* d_sigma, const uint64_t* d_z, uint32_t chunk_len,
+                                         uint64_t rows, const uint64_t omega_ext[4], const uint64_t shift[4],
+                                         const uint64_t delta[4], const uint64_t beta[4],
+                                         const uint64_t gamma[4], const uint64_t y[4],
+                                         const uint64_t* d_h_in, uint64_t* d_h_out, uint32_t form,
+                                         void* stream);
+
+/* Lookup terms. d_lookup holds the five columns A, S, A', S', z in the order
+ * b2f_lookup_columns_dev writes them, extended (stride rows). Terms per row, T = 5:
+ *   l_0 (1 - z)
+ *   l_last (z^2 - z)
+ *   l_active (z(w X) (A' + beta) (S' + gamma) - z (A + beta) (S + gamma))
+ *   l_0 (A' - S')
+ *   l_active (A' - S') (A' - A'(w^-1 X))
+ * A and S are passed compressed: the theta-combination is linear, so the extension of the
+ * compressed column is the polynomial halo2 evaluates, provided its blinding rows are the
+ * compression of the advice (and table) blinding rows. There is no theta argument. */
+B2F_API int b2f_quotient_lookup_dev(b2f_ctx* ctx, uint32_t k, uint32_t ext_k, const uint64_t* d_l,
+                                    const uint64_t* d_lookup, uint64_t rows, const uint64_t beta[4],
+                                    const uint64_t gamma[4], const uint64_t y[4], const uint64_t* d_h_in,
+                                    uint64_t* d_h_out, uint32_t form, void* stream);
+
+/* divide_by_vanishing_poly: h_out[i] = h_in[i] (X_i^n - 1)^-1 over the n_ext rows, in place
+ * allowed. The divisor has period rot in i: rot values are inverted on the device once per
+ * (field, k, ext_k, omega_ext, shift) and cached in the context (4 domains, replaced round-robin).
+ * B2F_ERR_FIELD at b2f_sync when X_i^n = 1 for some i (e.g. shift = 1: the outputs are then
+ * meaningless) or omega_ext^(n_ext / 2) != -1; the next call works normally. */
+B2F_API int b2f_quotient_divide_dev(b2f_ctx* ctx, uint32_t k, uint32_t ext_k, const uint64_t omega_ext[4],
+                                    const uint64_t shift[4], const uint64_t* d_h_in, uint64_t* d_h_out,
+                                    uint32_t form, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launch stream around every kernel the
  * fill/eval calls launch (no host synchronization while recording). b2f_set_timing(ctx, 1)
  * clears the log and starts recording; b2f_kernel_times waits for the recorded events and
@@ -401,10 +475,11 @@ B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_
 #define B2F_KERNEL_PERM 6   /* permutation-argument prover columns (all passes of one call) */
 #define B2F_KERNEL_PERM_SIGMA 7 /* permutation keygen: the sigma columns (b2f_permutation_sigma_dev) */
 #define B2F_KERNEL_NTT 8    /* NTT of prover columns (table build and all passes of one call) */
-#define B2F_NUM_KERNELS 9
+#define B2F_KERNEL_QUOTIENT 9 /* quotient terms, the vanishing divide, the Lagrange selectors */
+#define B2F_NUM_KERNELS 10
 /* total_ms and count must each hold b2f_num_kernels() entries (= B2F_NUM_KERNELS of the
- * header the library was built with; it grew from 7 to 8 with B2F_KERNEL_PERM_SIGMA and to 9
- * with B2F_KERNEL_NTT): a caller
+ * header the library was built with; it grew from 7 to 8 with B2F_KERNEL_PERM_SIGMA, to 9
+ * with B2F_KERNEL_NTT and to 10 with B2F_KERNEL_QUOTIENT): a caller
  * built against another header sizes its buffers from the query, so the library never writes
  * past them. */
 B2F_API int b2f_num_kernels(void);

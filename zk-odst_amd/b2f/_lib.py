@@ -26,7 +26,7 @@ CODE_LAYOUT = 19
 CODE_CHECK = 20  # an internal cross-check failed (B2F_ERR_CHECK): a library defect
 MAX_ROUNDS = 1 << 20
 KERNEL_NAMES = ["record", "fill", "eval", "export", "fill_eval", "lookup", "perm",
-                "perm_sigma", "ntt"]  # B2F_KERNEL_*
+                "perm_sigma", "ntt", "quotient"]  # B2F_KERNEL_*
 FP_CANONICAL, FP_MONTGOMERY, FP_BN254_CANONICAL, FP_BN254_MONTGOMERY = 0, 1, 2, 3  # B2F_FP_*
 NTT_FORWARD, NTT_INVERSE = 0, 1  # B2F_NTT_*
 
@@ -115,6 +115,14 @@ SIGNATURES = [
     ("b2f_permutation_sigma_dev", I32, [P, P, SIZE, ctypes.c_uint32, P, P, ctypes.c_uint32, P, U64, P]),
     ("b2f_ntt_columns_dev", I32, [P, P, U64, U64, ctypes.c_uint32, ctypes.c_uint32, P, P,
                                   ctypes.c_uint32, ctypes.c_uint32, P, U64, P]),
+    ("b2f_lagrange_selectors_dev", I32, [P, ctypes.c_uint32, U64, ctypes.c_uint32, P, U64, P]),
+    ("b2f_quotient_permutation_dev", I32, [P, ctypes.c_uint32, ctypes.c_uint32, U64, P, P, P, P,
+                                           ctypes.c_uint32, U64, P, P, P, P, P, P, P, P,
+                                           ctypes.c_uint32, P]),
+    ("b2f_quotient_lookup_dev", I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, P, U64, P, P, P, P, P,
+                                      ctypes.c_uint32, P]),
+    ("b2f_quotient_divide_dev", I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, P, P, P,
+                                      ctypes.c_uint32, P]),
     ("b2f_sync", I32, [P, P]),
     ("b2f_fill", I32, [P, P, SIZE, P, P, P]),
     ("b2f_eval", I32, [P, P, P, P, SIZE, U64, P]),

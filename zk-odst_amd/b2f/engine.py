@@ -242,6 +242,143 @@ class Engine:
                              out.data_ptr(), int(out.shape[1]), s)
         return out
 
+    # ---------------------------------------------------------------- quotient terms
+    @staticmethod
+    def _limbs(*vals):
+        return [(ctypes.c_uint64 * 4)(*[(int(v) >> (64 * i)) & (2**64 - 1) for i in range(4)])
+                for v in vals]
+
+    def lagrange_selectors_dev(self, k, usable_rows, form, d_out, out_rows, stream=0):
+        self._check(self.lib.b2f_lagrange_selectors_dev(self.ctx, int(k), int(usable_rows), int(form),
+                                                        _vp(d_out), int(out_rows), _vp(stream)))
+
+    def quotient_permutation_dev(self, k, ext_k, usable_rows, d_l, d_advice, d_sigma, d_z, chunk_len,
+                                 rows, omega_ext, shift, delta, beta, gamma, y, d_h_in, d_h_out, form,
+                                 stream=0):
+        """b2f_quotient_permutation_dev; omega_ext/shift/delta/beta/gamma/y are Python ints
+        (canonical), d_h_in 0 or None for a zero accumulator."""
+        lim = self._limbs(omega_ext, shift, delta, beta, gamma, y)
+        self._check(self.lib.b2f_quotient_permutation_dev(
+            self.ctx, int(k), int(ext_k), int(usable_rows), _vp(d_l), _vp(d_advice), _vp(d_sigma),
+            _vp(d_z), int(chunk_len), int(rows), lim[0], lim[1], lim[2], lim[3], lim[4], lim[5],
+            _vp(d_h_in) if d_h_in else None, _vp(d_h_out), int(form), _vp(stream)))
+
+    def quotient_lookup_dev(self, k, ext_k, d_l, d_lookup, rows, beta, gamma, y, d_h_in, d_h_out, form,
+                            stream=0):
+        """b2f_quotient_lookup_dev; beta/gamma/y are Python ints (canonical)."""
+        lim = self._limbs(beta, gamma, y)
+        self._check(self.lib.b2f_quotient_lookup_dev(
+            self.ctx, int(k), int(ext_k), _vp(d_l), _vp(d_lookup), int(rows), lim[0], lim[1], lim[2],
+            _vp(d_h_in) if d_h_in else None, _vp(d_h_out), int(form), _vp(stream)))
+
+    def quotient_divide_dev(self, k, ext_k, omega_ext, shift, d_h_in, d_h_out, form, stream=0):
+        """b2f_quotient_divide_dev; omega_ext/shift are Python ints (canonical)."""
+        lim = self._limbs(omega_ext, shift)
+        self._check(self.lib.b2f_quotient_divide_dev(
+            self.ctx, int(k), int(ext_k), lim[0], lim[1], _vp(d_h_in), _vp(d_h_out), int(form),
+            _vp(stream)))
+
+    @staticmethod
+    def _cols(name, t, n_cols, min_rows):
+        import torch
+
+        if t.dim() != 3 or t.shape[0] != n_cols or t.shape[1] < min_rows or t.shape[2] != 4 \
+                or t.dtype != torch.int64 or not t.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "%s must be contiguous int64 [%d, rows >= %d, 4]"
+                                % (name, n_cols, min_rows))
+
+    def _h(self, name, h, ext_k):
+        import torch
+
+        if h.dim() != 2 or h.shape[0] < (1 << ext_k) or h.shape[1] != 4 or h.dtype != torch.int64 \
+                or not h.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "%s must be contiguous int64 [rows >= 2^ext_k, 4]" % name)
+
+    def lagrange_selectors(self, k, usable_rows, form=_lib.FP_MONTGOMERY, device="cuda:0", stream=None):
+        """l_0, l_last, l_active in the Lagrange basis: int64 [3, 2^k, 4] in `form`
+        (b2f_lagrange_selectors_dev)."""
+        import torch
+
+        out = torch.empty((3, 1 << int(k), 4), dtype=torch.int64, device=device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.lagrange_selectors_dev(k, usable_rows, form, out.data_ptr(), 1 << int(k), s)
+        return out
+
+    def extend_columns(self, cols, k, ext_k, shift, form=_lib.FP_MONTGOMERY, stream=None):
+        """Lagrange-form columns over 2^k rows (int64 [n_cols, rows >= 2^k, 4]) to their
+        evaluations on the extended coset shift <omega_ext>: int64 [n_cols, 2^ext_k, 4]. The
+        inverse NTT with shift 1, then the forward one on the coset with in_len = 2^k."""
+        coeff = self.ntt_columns(cols, k, inverse=True, form=form, stream=stream)
+        return self.ntt_columns(coeff, ext_k, shift=shift, in_len=1 << int(k), form=form, stream=stream)
+
+    def quotient_permutation(self, k, ext_k, usable_rows, l, advice, sigma, z, chunk_len, shift, beta,
+                             gamma, y, h=None, out=None, form=_lib.FP_MONTGOMERY, stream=None):
+        """The permutation terms folded into h (b2f_quotient_permutation_dev). l [3, rows, 4],
+        advice [10, rows, 4], sigma [8, rows, 4], z [ceil(8 / chunk_len), rows, 4]: extended-coset
+        columns of one stride rows >= 2^ext_k, int64 in `form`. h: the accumulator so far ([rows >=
+        2^ext_k, 4]) or None for zero; out: where the result goes (default: h itself, in place, or
+        a new [2^ext_k, 4] tensor). The domain's omega_ext and the field's delta are the library's
+        (b2f.field); shift is the caller's. Returns the result tensor."""
+        import torch
+
+        from . import field
+
+        rows = int(l.shape[1]) if l.dim() == 3 else 0
+        sets = (8 + int(chunk_len) - 1) // max(int(chunk_len), 1)
+        for name, t, nc in (("l", l, 3), ("advice", advice, 10), ("sigma", sigma, 8), ("z", z, sets)):
+            self._cols("quotient_permutation: " + name, t, nc, 1 << int(ext_k))
+            if int(t.shape[1]) != rows:
+                raise _lib.B2FError(_lib.ERR_ARG, "quotient_permutation: the blocks must share one stride")
+        if h is not None:
+            self._h("quotient_permutation: h", h, ext_k)
+        if out is None:
+            out = h if h is not None else torch.empty((1 << int(ext_k), 4), dtype=torch.int64, device=l.device)
+        self._h("quotient_permutation: out", out, ext_k)
+        f = field.of_form(form)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.quotient_permutation_dev(k, ext_k, usable_rows, l.data_ptr(), advice.data_ptr(),
+                                      sigma.data_ptr(), z.data_ptr(), chunk_len, rows,
+                                      field.omega(f, int(ext_k)), shift, field.delta(f), beta, gamma, y,
+                                      h.data_ptr() if h is not None else 0, out.data_ptr(), form, s)
+        return out
+
+    def quotient_lookup(self, k, ext_k, l, lookup, beta, gamma, y, h=None, out=None,
+                        form=_lib.FP_MONTGOMERY, stream=None):
+        """The lookup terms folded into h (b2f_quotient_lookup_dev). l [3, rows, 4], lookup
+        [5, rows, 4] (A, S, A', S', z extended); h and out as in quotient_permutation."""
+        import torch
+
+        rows = int(l.shape[1]) if l.dim() == 3 else 0
+        for name, t, nc in (("l", l, 3), ("lookup", lookup, 5)):
+            self._cols("quotient_lookup: " + name, t, nc, 1 << int(ext_k))
+            if int(t.shape[1]) != rows:
+                raise _lib.B2FError(_lib.ERR_ARG, "quotient_lookup: the blocks must share one stride")
+        if h is not None:
+            self._h("quotient_lookup: h", h, ext_k)
+        if out is None:
+            out = h if h is not None else torch.empty((1 << int(ext_k), 4), dtype=torch.int64, device=l.device)
+        self._h("quotient_lookup: out", out, ext_k)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.quotient_lookup_dev(k, ext_k, l.data_ptr(), lookup.data_ptr(), rows, beta, gamma, y,
+                                 h.data_ptr() if h is not None else 0, out.data_ptr(), form, s)
+        return out
+
+    def quotient_divide(self, k, ext_k, shift, h, out=None, form=_lib.FP_MONTGOMERY, stream=None):
+        """h / (X^n - 1) on the extended coset (b2f_quotient_divide_dev): updates h in place, or
+        writes `out` when given. Returns the result tensor."""
+        import torch
+
+        from . import field
+
+        self._h("quotient_divide: h", h, ext_k)
+        if out is None:
+            out = h
+        self._h("quotient_divide: out", out, ext_k)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.quotient_divide_dev(k, ext_k, field.omega(field.of_form(form), int(ext_k)), shift,
+                                 h.data_ptr(), out.data_ptr(), form, s)
+        return out
+
     def debug_eval_path(self):
         """Path of the last eval_dev call (device-synchronizing): 0 the fast clean-check pass
         found the trace clean, 1 it flagged something and the exact eval kernel reported, 2 no

@@ -232,6 +232,49 @@ __device__ __forceinline__ Fe add(const Fe& a, const Fe& b) {  // a + b < 2p < 2
   return reduce_once<F>(s);
 }
 
+// a - b mod p (a, b < p); on Montgomery forms it is the Montgomery form of the difference
+template <class F>
+__device__ __forceinline__ Fe sub(const Fe& a, const Fe& b) {
+  Fe d;
+  uint32_t br = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint64_t x = (uint64_t)a.w[i] - b.w[i] - br;
+    d.w[i] = (uint32_t)x;
+    br = (uint32_t)(x >> 63);
+  }
+  Fe e;
+  uint32_t c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint64_t x = (uint64_t)d.w[i] + F::P[i] + c;
+    e.w[i] = (uint32_t)x;
+    c = (uint32_t)(x >> 32);
+  }
+  return br ? e : d;
+}
+
+__device__ __forceinline__ bool fe_eq(const Fe& a, const Fe& b) {
+  uint32_t o = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) o |= a.w[i] ^ b.w[i];
+  return o == 0;
+}
+
+// base^e (Montgomery form), left-to-right square and multiply
+template <class F>
+__device__ Fe fe_pow(const Fe& base, uint32_t e) {
+  Fe acc = one<F>();
+  if (!e) return acc;
+  int top = 31 - __builtin_clz(e);
+#pragma unroll 1
+  for (int b = top; b >= 0; b--) {
+    acc = mul<F>(acc, acc);
+    if ((e >> b) & 1u) acc = mul<F>(acc, base);
+  }
+  return acc;
+}
+
 // Montgomery form of a small integer, x R mod p, without a Montgomery product: with c = R mod p
 // (F::R), x c < 2^32 p, so the quotient fits 32 bits and q' = floor(x RQ / 2^64) is q or q - 1
 // (x c / p - x RQ / 2^64 < x / 2^64 < 1). x c - q' p is in [0, 2p): computed mod 2^256 as 16

@@ -71,6 +71,27 @@ hipError_t launch_ntt_tables(void* d_tab, uint32_t form, uint32_t k, const uint6
 hipError_t launch_ntt(const uint64_t* d_in, uint64_t in_rows, uint64_t in_len, uint32_t n_cols,
                       uint32_t k, uint32_t form, uint32_t direction, bool shift_is_one, uint64_t* d_out,
                       uint64_t out_rows, const void* d_tab, int* sticky, hipStream_t s);
+size_t quot_xtab_bytes(uint32_t ext_k);  // b2f_quotient.hip
+size_t quot_consts_bytes();
+hipError_t launch_quot_xtab(void* d_tab, uint32_t form, uint32_t ext_k, const uint64_t* omega,
+                            const uint64_t* shift, hipStream_t s);
+hipError_t launch_lagrange_selectors(uint32_t k, uint32_t usable_rows, uint32_t form, uint64_t* d_out,
+                                     uint64_t out_rows, hipStream_t s);
+hipError_t launch_quot_permutation(uint32_t k, uint32_t ext_k, uint32_t usable_rows, const uint64_t* d_l,
+                                   const uint64_t* d_advice, const uint64_t* d_sigma, const uint64_t* d_z,
+                                   uint32_t chunk_len, uint64_t rows, const uint64_t* delta,
+                                   const uint64_t* beta, const uint64_t* gamma, const uint64_t* y,
+                                   const uint64_t* d_h_in, uint64_t* d_h_out, uint32_t form, uint32_t colmap,
+                                   const void* d_xtab, void* d_consts, int* sticky, hipStream_t s);
+hipError_t launch_quot_lookup(uint32_t k, uint32_t ext_k, const uint64_t* d_l, const uint64_t* d_lookup,
+                              uint64_t rows, const uint64_t* beta, const uint64_t* gamma, const uint64_t* y,
+                              const uint64_t* d_h_in, uint64_t* d_h_out, uint32_t form, void* d_consts,
+                              hipStream_t s);
+size_t quot_divisor_bytes(uint32_t k, uint32_t ext_k);
+hipError_t launch_quot_divisors(void* d_dtab, uint32_t form, uint32_t k, uint32_t ext_k, const uint64_t* omega,
+                                const uint64_t* shift, hipStream_t s);
+hipError_t launch_quot_divide(uint32_t k, uint32_t ext_k, const uint64_t* d_h_in, uint64_t* d_h_out,
+                              uint32_t form, const void* d_dtab, int* sticky, hipStream_t s);
 hipError_t launch_export_fp(const uint32_t* d_advice, uint64_t total_rows, uint64_t row_begin,
                             uint64_t nrows, uint32_t form, uint64_t* d_out, uint64_t out_rows,
                             int cu_count, unsigned* tctr, hipStream_t s);  // b2f_export.hip
@@ -990,6 +1011,21 @@ struct b2f_ctx {
   static constexpr int NTT_TABS = 8;
   NttTab ntt_tab[NTT_TABS];
   uint32_t ntt_next;
+  // quotient terms (b2f_quotient.hip): the X_i tables, one block per (field, ext_k, omega, shift)
+  // seen, and the inverse divisors of the vanishing divide, one block per (field, k, ext_k, omega,
+  // shift) seen (k = 0 in the X_i entries); both replaced round-robin as the NTT's are. And the
+  // per-call challenge constants.
+  struct QuotTab {
+    uint32_t field, k, ext_k;
+    uint64_t omega[4], shift[4];
+    void* d;
+    size_t cap;
+    bool live;
+  };
+  static constexpr int QUOT_TABS = 4;
+  QuotTab quot_tab[QUOT_TABS], quot_div[QUOT_TABS];
+  uint32_t quot_next, quot_div_next;
+  void* d_quot_consts;
 };
 
 namespace {
@@ -1267,6 +1303,9 @@ B2F_API void b2f_destroy(b2f_ctx* ctx) {
   (void)hipFree(ctx->d_pm_inst);
   (void)hipFree(ctx->d_pm);
   for (auto& t : ctx->ntt_tab) (void)hipFree(t.d);
+  for (auto& t : ctx->quot_tab) (void)hipFree(t.d);
+  for (auto& t : ctx->quot_div) (void)hipFree(t.d);
+  (void)hipFree(ctx->d_quot_consts);
   if (ctx->pm_inst_ev_live) (void)hipEventSynchronize(ctx->pm_inst_ev);
   if (ctx->pm_inst_ev) (void)hipEventDestroy(ctx->pm_inst_ev);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
@@ -1960,6 +1999,206 @@ B2F_API int b2f_permutation_sigma_dev(b2f_ctx* ctx, const uint64_t* h_offsets, s
   return B2F_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// v < p for the field `form` selects (4 little-endian u64 limbs)
+bool fe_canonical(uint32_t form, const uint64_t* v) {
+  static const uint64_t moduli[2][4] = {
+      {0x992d30ed00000001ull, 0x224698fc094cf91bull, 0, 0x4000000000000000ull},
+      {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull}};
+  const uint64_t* p = moduli[(form >> 1) & 1u];
+  for (int i = 3; i >= 0; i--)
+    if (v[i] != p[i]) return v[i] < p[i];
+  return false;
+}
+bool fe_is_zero(const uint64_t* v) { return !(v[0] | v[1] | v[2] | v[3]); }
+
+// [a, a + an) and [b, b + bn) share a byte
+bool ranges_overlap(const void* a, uint64_t an, const void* b, uint64_t bn) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + bn && b0 < a0 + an;
+}
+
+// The checks the term calls and the divide share; `what` names the call in messages.
+int quot_check_common(b2f_ctx* ctx, const char* what, uint32_t k, uint32_t ext_k, uint64_t rows, uint32_t form,
+                      const uint64_t* d_h_in, const uint64_t* d_h_out) {
+  if (!d_h_out) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (((uintptr_t)d_h_in | (uintptr_t)d_h_out) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "%s: buffers must be 16-byte aligned", what);
+  if (k < 1 || ext_k > 28 || k >= ext_k)
+    return set_err(ctx, B2F_ERR_ARG, "%s: need 1 <= k < ext_k <= 28, got k %u, ext_k %u", what, k, ext_k);
+  if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "%s: unknown form %u", what, form);
+  if (rows < (1ull << ext_k)) return set_err(ctx, B2F_ERR_ROWS, "%s: rows < 2^ext_k", what);
+  if (rows > (1ull << 52)) return set_err(ctx, B2F_ERR_ARG, "%s: column stride overflows the address space", what);
+  const uint64_t hb = 32ull << ext_k;
+  if (d_h_in && d_h_in != d_h_out && ranges_overlap(d_h_in, hb, d_h_out, hb))
+    return set_err(ctx, B2F_ERR_ARG, "%s: h_in and h_out overlap without being equal", what);
+  return B2F_OK;
+}
+
+// The cached block of a domain in `tabs`, or nullptr with *slot = the entry to fill (its buffer
+// grown to `need` bytes, not yet live).
+int quot_tab_find(b2f_ctx* ctx, b2f_ctx::QuotTab* tabs, uint32_t* next, uint32_t form, uint32_t k,
+                  uint32_t ext_k, const uint64_t* omega, const uint64_t* shift, size_t need, hipStream_t s,
+                  b2f_ctx::QuotTab** found, b2f_ctx::QuotTab** slot) {
+  *found = *slot = nullptr;
+  for (int i = 0; i < b2f_ctx::QUOT_TABS; i++) {
+    b2f_ctx::QuotTab& t = tabs[i];
+    if (t.live && t.field == (form >> 1) && t.k == k && t.ext_k == ext_k && !memcmp(t.omega, omega, 32) &&
+        !memcmp(t.shift, shift, 32))
+      *found = &t;
+  }
+  if (*found) return B2F_OK;
+  b2f_ctx::QuotTab& t = tabs[(*next)++ % b2f_ctx::QUOT_TABS];
+  t.live = false;
+  if (need > t.cap) {  // earlier calls on the stream may still read the block
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (t.d) HIPCHK(ctx, hipFree(t.d));
+    t.d = nullptr;
+    t.cap = 0;
+    HIPCHK(ctx, hipMalloc(&t.d, need));
+    t.cap = need;
+  }
+  t.field = form >> 1;
+  t.k = k;
+  t.ext_k = ext_k;
+  memcpy(t.omega, omega, 32);
+  memcpy(t.shift, shift, 32);
+  *slot = &t;
+  return B2F_OK;
+}
+
+// the per-call constant block of the term calls
+int quot_consts(b2f_ctx* ctx) {
+  if (!ctx->d_quot_consts) HIPCHK(ctx, hipMalloc(&ctx->d_quot_consts, quot_consts_bytes()));
+  return B2F_OK;
+}
+}  // namespace
+
+extern "C" {
+
+B2F_API int b2f_lagrange_selectors_dev(b2f_ctx* ctx, uint32_t k, uint64_t usable_rows, uint32_t form,
+                                       uint64_t* d_out, uint64_t out_rows, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  if (!d_out) return set_err(ctx, B2F_ERR_ARG, "selectors: null buffer");
+  if ((uintptr_t)d_out & 15) return set_err(ctx, B2F_ERR_ARG, "selectors: d_out must be 16-byte aligned");
+  if (k < 1 || k > 28) return set_err(ctx, B2F_ERR_ARG, "selectors: k %u not in [1, 28]", k);
+  if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "selectors: unknown form %u", form);
+  if (usable_rows >= (1ull << k))
+    return set_err(ctx, B2F_ERR_ROWS, "selectors: usable_rows %llu >= 2^k", (unsigned long long)usable_rows);
+  if (out_rows < (1ull << k)) return set_err(ctx, B2F_ERR_ROWS, "selectors: out_rows < 2^k");
+  if (out_rows > (1ull << 52)) return set_err(ctx, B2F_ERR_ARG, "selectors: column stride overflows the address space");
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_lagrange_selectors(k, (uint32_t)usable_rows, form, d_out, out_rows, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API int b2f_quotient_permutation_dev(b2f_ctx* ctx, uint32_t k, uint32_t ext_k, uint64_t usable_rows,
+                                         const uint64_t* d_l, const uint64_t* d_advice,
+                                         const uint64_t* d_sigma, const uint64_t* d_z, uint32_t chunk_len,
+                                         uint64_t rows, const uint64_t omega_ext[4], const uint64_t shift[4],
+                                         const uint64_t delta[4], const uint64_t beta[4],
+                                         const uint64_t gamma[4], const uint64_t y[4],
+                                         const uint64_t* d_h_in, uint64_t* d_h_out, uint32_t form,
+                                         void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "quotient permutation";
+  if (!d_l || !d_advice || !d_sigma || !d_z || !omega_ext || !shift || !delta || !beta || !gamma || !y)
+    return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (((uintptr_t)d_l | (uintptr_t)d_advice | (uintptr_t)d_sigma | (uintptr_t)d_z) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "%s: buffers must be 16-byte aligned", what);
+  if (int rc = quot_check_common(ctx, what, k, ext_k, rows, form, d_h_in, d_h_out)) return rc;
+  if (chunk_len < 1 || chunk_len > 8) return set_err(ctx, B2F_ERR_ARG, "%s: chunk_len %u not in [1, 8]", what, chunk_len);
+  const uint64_t* elems[6] = {omega_ext, shift, delta, beta, gamma, y};
+  for (const uint64_t* e : elems)
+    if (!fe_canonical(form, e)) return set_err(ctx, B2F_ERR_ARG, "%s: a challenge, omega, shift or delta is >= p", what);
+  if (fe_is_zero(shift)) return set_err(ctx, B2F_ERR_ARG, "%s: shift is zero", what);
+  if (usable_rows >= (1ull << k))
+    return set_err(ctx, B2F_ERR_ROWS, "%s: usable_rows %llu >= 2^k", what, (unsigned long long)usable_rows);
+  const uint32_t sets = (8 + chunk_len - 1) / chunk_len;
+  const uint64_t hb = 32ull << ext_k;
+  if (ranges_overlap(d_h_out, hb, d_l, 3 * rows * 32) || ranges_overlap(d_h_out, hb, d_advice, 10 * rows * 32) ||
+      ranges_overlap(d_h_out, hb, d_sigma, 8 * rows * 32) || ranges_overlap(d_h_out, hb, d_z, sets * rows * 32))
+    return set_err(ctx, B2F_ERR_ARG, "%s: h_out overlaps an input block", what);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = quot_consts(ctx)) return rc;
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  b2f_ctx::QuotTab *tab, *slot;
+  if (int rc = quot_tab_find(ctx, ctx->quot_tab, &ctx->quot_next, form, 0, ext_k, omega_ext, shift,
+                             quot_xtab_bytes(ext_k), s, &tab, &slot))
+    return rc;
+  if (!tab) {
+    HIPCHK(ctx, launch_quot_xtab(slot->d, form, ext_k, omega_ext, shift, s));
+    slot->live = true;
+    tab = slot;
+  }
+  uint32_t colmap = 0;  // v_j = the advice column of a_{j+1}
+  for (int j = 0; j < 8; j++) colmap |= (uint32_t)b2f_halo2_column_index(j + 1) << (4 * j);
+  HIPCHK(ctx, launch_quot_permutation(k, ext_k, (uint32_t)usable_rows, d_l, d_advice, d_sigma, d_z, chunk_len,
+                                      rows, delta, beta, gamma, y, d_h_in, d_h_out, form, colmap, tab->d,
+                                      ctx->d_quot_consts, ctx->d_status + 2, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API int b2f_quotient_lookup_dev(b2f_ctx* ctx, uint32_t k, uint32_t ext_k, const uint64_t* d_l,
+                                    const uint64_t* d_lookup, uint64_t rows, const uint64_t beta[4],
+                                    const uint64_t gamma[4], const uint64_t y[4], const uint64_t* d_h_in,
+                                    uint64_t* d_h_out, uint32_t form, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "quotient lookup";
+  if (!d_l || !d_lookup || !beta || !gamma || !y) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (((uintptr_t)d_l | (uintptr_t)d_lookup) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "%s: buffers must be 16-byte aligned", what);
+  if (int rc = quot_check_common(ctx, what, k, ext_k, rows, form, d_h_in, d_h_out)) return rc;
+  if (!fe_canonical(form, beta) || !fe_canonical(form, gamma) || !fe_canonical(form, y))
+    return set_err(ctx, B2F_ERR_ARG, "%s: a challenge is >= p", what);
+  const uint64_t hb = 32ull << ext_k;
+  if (ranges_overlap(d_h_out, hb, d_l, 3 * rows * 32) || ranges_overlap(d_h_out, hb, d_lookup, 5 * rows * 32))
+    return set_err(ctx, B2F_ERR_ARG, "%s: h_out overlaps an input block", what);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = quot_consts(ctx)) return rc;
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_quot_lookup(k, ext_k, d_l, d_lookup, rows, beta, gamma, y, d_h_in, d_h_out, form,
+                                 ctx->d_quot_consts, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API int b2f_quotient_divide_dev(b2f_ctx* ctx, uint32_t k, uint32_t ext_k, const uint64_t omega_ext[4],
+                                    const uint64_t shift[4], const uint64_t* d_h_in, uint64_t* d_h_out,
+                                    uint32_t form, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "quotient divide";
+  if (!d_h_in || !omega_ext || !shift) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  const uint64_t n_ext = ext_k <= 28 ? 1ull << ext_k : 0;  // an ext_k out of range: the check reports it
+  if (int rc = quot_check_common(ctx, what, k, ext_k, n_ext, form, d_h_in, d_h_out)) return rc;
+  if (!fe_canonical(form, omega_ext) || !fe_canonical(form, shift))
+    return set_err(ctx, B2F_ERR_ARG, "%s: omega or shift is >= p", what);
+  if (fe_is_zero(shift)) return set_err(ctx, B2F_ERR_ARG, "%s: shift is zero", what);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  b2f_ctx::QuotTab *tab, *slot;
+  if (int rc = quot_tab_find(ctx, ctx->quot_div, &ctx->quot_div_next, form, k, ext_k, omega_ext, shift,
+                             quot_divisor_bytes(k, ext_k), s, &tab, &slot))
+    return rc;
+  if (!tab) {
+    HIPCHK(ctx, launch_quot_divisors(slot->d, form, k, ext_k, omega_ext, shift, s));
+    slot->live = true;
+    tab = slot;
+  }
+  HIPCHK(ctx, launch_quot_divide(k, ext_k, d_h_in, d_h_out, form, tab->d, ctx->d_status + 2, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
 B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_rows,
                                 uint64_t in_len, uint32_t n_cols, uint32_t k,
                                 const uint64_t omega[4], const uint64_t shift[4],
@@ -1973,18 +2212,9 @@ B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_
   if (n_cols == 0 || in_len == 0) return set_err(ctx, B2F_ERR_ARG, "ntt: no columns or no input rows");
   if (direction > B2F_NTT_INVERSE) return set_err(ctx, B2F_ERR_ARG, "ntt: unknown direction %u", direction);
   if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "ntt: unknown form %u", form);
-  static const uint64_t moduli[2][4] = {
-      {0x992d30ed00000001ull, 0x224698fc094cf91bull, 0, 0x4000000000000000ull},
-      {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull}};
-  auto canon = [&](const uint64_t* v) {
-    const uint64_t* p = moduli[form >> 1];
-    for (int i = 3; i >= 0; i--)
-      if (v[i] != p[i]) return v[i] < p[i];
-    return false;
-  };
-  if (!canon(omega) || !canon(shift))
+  if (!fe_canonical(form, omega) || !fe_canonical(form, shift))
     return set_err(ctx, B2F_ERR_ARG, "ntt: omega/shift not canonical field elements");
-  if (!(shift[0] | shift[1] | shift[2] | shift[3])) return set_err(ctx, B2F_ERR_ARG, "ntt: shift is zero");
+  if (fe_is_zero(shift)) return set_err(ctx, B2F_ERR_ARG, "ntt: shift is zero");
   const uint64_t n_rows = 1ull << k;
   if (in_len > n_rows) return set_err(ctx, B2F_ERR_ROWS, "ntt: in_len %llu > 2^k", (unsigned long long)in_len);
   if (in_rows < in_len) return set_err(ctx, B2F_ERR_ROWS, "ntt: in_rows < in_len");

@@ -80,34 +80,6 @@ struct NttPass {
 
 __host__ __device__ inline uint32_t ntt_h0(uint32_t k) { return (k + 1) / 2; }
 
-template <class F>
-__device__ __forceinline__ Fe sub(const Fe& a, const Fe& b) {  // a - b mod p (a, b < p)
-  Fe d;
-  uint32_t br = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    const uint64_t x = (uint64_t)a.w[i] - b.w[i] - br;
-    d.w[i] = (uint32_t)x;
-    br = (uint32_t)(x >> 63);
-  }
-  Fe e;
-  uint32_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    const uint64_t x = (uint64_t)d.w[i] + F::P[i] + c;
-    e.w[i] = (uint32_t)x;
-    c = (uint32_t)(x >> 32);
-  }
-  return br ? e : d;
-}
-
-__device__ __forceinline__ bool fe_eq(const Fe& a, const Fe& b) {
-  uint32_t o = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) o |= a.w[i] ^ b.w[i];
-  return o == 0;
-}
-
 __device__ __forceinline__ Fe tab_load(const uint64_t* tab, uint32_t idx) { return load(tab + 4ull * idx); }
 
 // One lane: the inverses, the derived roots and the primitive-root check.
@@ -140,19 +112,6 @@ __global__ void ntt_setup_kernel(uint64_t* tab, Words4 omega, Words4 shift, uint
   H.bad = bad ? 1u : 0u;
   for (int i = 0; i < 15; i++) H.pad[i] = 0;
   *reinterpret_cast<NttHeader*>(tab) = H;
-}
-
-template <class F>
-__device__ Fe fe_pow(const Fe& base, uint32_t e) {
-  Fe acc = one<F>();
-  if (!e) return acc;
-  int top = 31 - __builtin_clz(e);
-#pragma unroll 1
-  for (int b = top; b >= 0; b--) {
-    acc = mul<F>(acc, acc);
-    if ((e >> b) & 1u) acc = mul<F>(acc, base);
-  }
-  return acc;
 }
 
 // One lane per table entry.
