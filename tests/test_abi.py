@@ -115,12 +115,58 @@ def test_product_library_reads_no_environment():
 
     prod = open(_lib.LIB_PATH, "rb").read()
     diag = open(_lib.DIAG_LIB_PATH, "rb").read()
-    for var in (b"B2F_DIAG_EVAL", b"B2F_DIAG_FILL", b"B2F_DIAG_FUSED", b"B2F_FILL_WGS"):
+    for var in (b"B2F_DIAG_EVAL", b"B2F_DIAG_FILL", b"B2F_DIAG_FUSED", b"B2F_FILL_WGS",
+                b"B2F_DIAG_NTT_PLAN", b"b2f_debug_field_op", b"b2f_debug_ntt_plan"):
         assert var not in prod, var
         assert var in diag, var
     lib = _lib.load(diag=True)
     for name, _, _ in _lib.SIGNATURES:
         assert hasattr(lib, name), name
+    # the test hooks are exports of the diagnostics library alone
+    prod_lib = _lib.load()
+    for name, _, _ in _lib.DIAG_SIGNATURES:
+        assert hasattr(lib, name), name
+        assert not hasattr(prod_lib, name), name
+
+
+def test_ntt_pass_plan_table():
+    """The product's pass plan for every k (b2f_debug_ntt_plan, host only): one pass up to k = 10,
+    then ceil(k / 8) passes of digits <= 8, non-increasing, differing by at most 1, summing to k.
+    With B2F_DIAG_NTT_PLAN set, the export reports the forced plan or refuses as the call would."""
+    import os
+
+    from b2f import B2FError, _lib
+
+    assert "B2F_DIAG_NTT_PLAN" not in os.environ
+    for k in range(1, 29):
+        l = _lib.debug_ntt_plan(k)
+        assert len(l) == (1 if k <= 10 else -(-k // 8)), (k, l)
+        assert sum(l) == k and all(1 <= d for d in l), (k, l)
+        if k > 10:
+            assert max(l) <= 8 and max(l) - min(l) <= 1 and l == sorted(l, reverse=True), (k, l)
+    assert _lib.debug_ntt_plan(25) == [7, 6, 6, 6] and _lib.debug_ntt_plan(28) == [7, 7, 7, 7]
+    for k in (0, 29):
+        with pytest.raises(B2FError):
+            _lib.debug_ntt_plan(k)
+    try:
+        os.environ["B2F_DIAG_NTT_PLAN"] = "3,3,3,2"
+        assert _lib.debug_ntt_plan(11) == [3, 3, 3, 2]
+        for k in (10, 12):  # the sum is not k
+            with pytest.raises(B2FError) as e:
+                _lib.debug_ntt_plan(k)
+            assert e.value.code == _lib.ERR_ARG
+        for bad, k in (("", 11), ("11", 11), ("6,5,", 11), ("6, 5", 11), ("0,8,3", 11), ("9,2", 11),
+                       ("3,2,2,2,2", 11), ("5,5", 10), ("10", 10), ("6,5x", 11), ("-6,5", 11),
+                       ("06,5", 11), ("8,8,8,8", 28 + 4)):
+            os.environ["B2F_DIAG_NTT_PLAN"] = bad
+            with pytest.raises(B2FError) as e:
+                _lib.debug_ntt_plan(k)
+            assert e.value.code == _lib.ERR_ARG, (bad, k)
+        os.environ["B2F_DIAG_NTT_PLAN"] = "8,8,8,1"
+        assert _lib.debug_ntt_plan(25) == [8, 8, 8, 1]
+    finally:
+        os.environ.pop("B2F_DIAG_NTT_PLAN", None)
+    assert _lib.debug_ntt_plan(11) == [6, 5]
 
 
 @pytest.mark.parametrize("rounds", [0, 1, 2, 12, 13])

@@ -6,10 +6,15 @@ tests/test_ntt_ref.py pins to the O(n^2) definition).
   2  every k from 7 to 16, every row against the reference;
   3  zero padding (in_len < n) with a cube-root-of-unity shift, garbage past in_len;
   4  each pass plan at scale. One pass: k <= 10; two passes: k = 11..16; three passes:
-     k = 17..24 (four: k = 25..28, 1 GiB per column and more, not run here). The smallest and the
-     largest k of each plan up to k = 23: a sparse input against its six-term direct sum, and
-     inverse(forward(x)) == x on a dense input;
-  5  65,537 columns at k = 1; 130 columns at k = 10 against single-column calls;
+     k = 17..24; four: k = 25..28. The smallest and the largest k of each plan up to k = 25: a
+     sparse input against its six-term direct sum, and inverse(forward(x)) == x on a dense input.
+     Four passes run at k = 25 (1 GiB per column); k = 26..28 run the same code with wider digits
+     and stay unrun here (2 to 8 GiB per column): no 32-bit quantity in the kernel grows past
+     2^28 (row indices, digit values, twiddle exponents after their mask), and the exponent
+     products are formed in 64 bits. tests/test_gpu_ntt_plans.py runs three- and four-pass plans
+     at k = 11..16 against the reference on every row;
+  5  65,537 columns at k = 1; 130 columns at k = 10 against single-column calls; three columns
+     with padded strides at k = 11 and k = 17 (two and three passes), in_len = n / 4;
   6  the permutation z column of a k = 10 circuit: to coefficients and to an extended coset;
   7  the table cache: domains alternate, another generator of the same domain;
   8  every argument error of the header, the primitive-root check at sync;
@@ -191,7 +196,7 @@ def _random_device(n_cols, rows, seed):
     return x
 
 
-@pytest.mark.parametrize("k", [1, 10, 11, 16, 17, 23])
+@pytest.mark.parametrize("k", [1, 10, 11, 16, 17, 23, 24, 25])
 def test_pass_plans(engine, k):
     import torch
 
@@ -265,6 +270,37 @@ def test_columns_equal_single_column_calls(engine):
             vals = nr.unpack(hx[c], form)
             want = nr.pack(_expect(vals, n, k, INV if inverse else FWD, shift, form), form)
             assert _first_diff(hout[c], want) is None, (inverse, c)
+
+
+@pytest.mark.parametrize("k", [11, 17])
+def test_padded_strides_on_multi_pass_sizes(engine, k):
+    """Several columns whose strides are not n, where every pass after the first works in place on
+    the output: each column equals its own single-column call, rows past n are never written, and
+    at k = 11 every row equals the reference."""
+    import torch
+
+    form = 1 if k == 11 else 2
+    p = nr.modulus(form)
+    n, n_cols = 1 << k, 3
+    in_rows, out_rows = n + 3, n + 5
+    rng = np.random.default_rng(520 + k)
+    shift = _shift(rng, p)
+    x = _random_device(n_cols, in_rows, 5200 + k)
+    pat = _dev(_pattern((n_cols, out_rows, 4)))
+    for inverse, in_len in ((False, n // 4), (True, n)):
+        out = engine.ntt_columns(x, k, inverse=inverse, shift=shift, in_len=in_len, form=form, out=pat.clone())
+        single = [engine.ntt_columns(x[c:c + 1], k, inverse=inverse, shift=shift, in_len=in_len, form=form,
+                                     out=pat[:1].clone()) for c in range(n_cols)]
+        engine.sync(_stream())
+        assert torch.equal(out, torch.cat(single)), inverse
+        assert torch.equal(out[:, n:], pat[:, n:]), inverse
+        assert not torch.equal(out[0, :n], out[1, :n])
+        if k == 11:
+            hx, hout = _host(x), _host(out)
+            for c in range(n_cols):
+                vals = nr.unpack(hx[c], form)
+                want = nr.pack(_expect(vals, in_len, k, INV if inverse else FWD, shift, form), form)
+                assert _first_diff(hout[c, :n], want) is None, (inverse, c)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -3,8 +3,8 @@
 * the committed header is exactly what tools/gen_mont_asm.py writes;
 * the instruction streams it emits, run by a small interpreter of the VALU instructions they use
   (one lane, vcc as a bit), give a b / 2^256 mod p for random and edge operands of both fields,
-  checked against Python integers. The GPU check of the same code is tools/mulbench.hip's
-  mismatch count and every field test of tests/test_gpu_*.py.
+  checked against Python integers. The GPU check of the same code on the same edge and crafted
+  operands is tests/test_gpu_field.py; tools/mulbench.hip counts mismatches on random ones.
 """
 import importlib.util
 import os
@@ -151,5 +151,26 @@ def test_generated_product_matches_integers():
         rinv = pow(1 << 256, -1, p)
         cases = [(0, 0), (1, 1), (p - 1, p - 1), (p - 1, 1), (0, p - 1)]
         cases += [(rng.randrange(p), rng.randrange(p)) for _ in range(300)]
+        for a, b in cases:
+            assert _mont(g, pw, np_, a, b) == a * b * rinv % p, (hex(a), hex(b))
+
+
+def test_generated_product_on_edge_pairs_and_crafted_reduction_words():
+    """The operands tests/test_gpu_field.py gives the device (tests/field_cases.py): E x E, and
+    products built to have a chosen reduction word m_k (0: pallas' no-borrow shortcut; 2^32 - 1;
+    the split of m_i 2^254; a result in [p, 2p)), both operand orders."""
+    import field_cases as fc
+
+    g = _gen()
+    for pw, np_ in ((g.PALLAS_P, g.PALLAS_NP), (g.BN254_P, g.BN254_NP)):
+        p = _val(pw)
+        assert p in fc.MODULI
+        rinv = pow(1 << 256, -1, p)
+        crafted = fc.crafted_pairs(p)
+        assert len(crafted) >= fc.CRAFT_MIN_FOUND, (len(crafted), fc.CRAFT_TARGETS)
+        carry = fc.carry_pairs(p)  # a column's high word all ones when its low word cancels
+        assert len(carry) >= fc.CARRY_MIN_FOUND, (len(carry), fc.CARRY_TARGETS)
+        cases = fc.edge_pairs(p) + [(c[3], c[4]) for c in crafted] + [(c[4], c[3]) for c in crafted]
+        cases += [(c[1], c[2]) for c in carry]
         for a, b in cases:
             assert _mont(g, pw, np_, a, b) == a * b * rinv % p, (hex(a), hex(b))

@@ -131,6 +131,15 @@ SIGNATURES = [
     ("b2f_kernel_times", I32, [P, P, P]),
 ]
 
+# Exports of libb2f_diag.so alone (not in include/b2f.h, not in libb2f.so): test hooks.
+DIAG_SIGNATURES = [
+    ("b2f_debug_field_op", I32, [ctypes.c_uint32, ctypes.c_uint32, P, P, SIZE, P, P]),
+    ("b2f_debug_ntt_plan", I32, [ctypes.c_uint32, P]),
+]
+# op codes of b2f_debug_field_op (csrc/b2f_fieldprobe.hip)
+FIELD_OPS = ["mul", "mul_comba", "mul_cios", "add", "sub", "from_u32", "to_mont", "to_canonical",
+             "fe_pow", "inv", "inv_kaliski", "inv_safegcd", "inv_fermat"]
+
 _libs = {}
 
 
@@ -165,8 +174,25 @@ def load(diag=False, path=None):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, res, args in DIAG_SIGNATURES:
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
     _libs[path] = lib
     return lib
+
+
+def debug_ntt_plan(k):
+    """Diagnostics build only, host only (b2f_debug_ntt_plan): the digits [l_1, .., l_P] of the pass
+    plan b2f_ntt_columns_dev runs a 2^k transform with under the current environment
+    (B2F_DIAG_NTT_PLAN); B2FError(ERR_ARG) where the call would be refused."""
+    out = (ctypes.c_uint32 * 5)()
+    rc = load(diag=True).b2f_debug_ntt_plan(int(k), out)
+    if rc != OK:
+        raise B2FError(rc, "no pass plan for k = %d under B2F_DIAG_NTT_PLAN=%r"
+                       % (k, os.environ.get("B2F_DIAG_NTT_PLAN")))
+    return [int(v) for v in out[1:1 + out[0]]]
 
 
 def check(ctx, rc, lib=None):

@@ -387,6 +387,22 @@ class Engine:
         self._check(self.lib.b2f_debug_eval_path(self.ctx, ctypes.byref(out)))
         return int(out.value)
 
+    def debug_field_op(self, op, a, b, field):
+        """Diagnostics build only (b2f_debug_field_op): the field primitive `op` (a name of
+        _lib.FIELD_OPS) on the device, one lane per element. a, b: uint64 [n, 4] host limbs, used as
+        given; field: 0 pallas, 1 BN254. Returns (out uint64 [n, 4], flags uint32 [n])."""
+        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
+        b = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 4)
+        if len(a) != len(b):
+            raise _lib.B2FError(_lib.ERR_ARG, "debug_field_op: a and b differ in length")
+        out = np.zeros_like(a)
+        flags = np.zeros(len(a), dtype=np.uint32)
+        rc = self.lib.b2f_debug_field_op(int(field), _lib.FIELD_OPS.index(op), _np_ptr(a), _np_ptr(b),
+                                         len(a), _np_ptr(out), _np_ptr(flags))
+        if rc != _lib.OK:
+            raise _lib.B2FError(rc, "debug_field_op(%s) refused or failed" % op)
+        return out, flags
+
     def sync(self, stream=0):
         self._check(self.lib.b2f_sync(self.ctx, _vp(stream)))
 

@@ -70,7 +70,9 @@ hipError_t launch_ntt_tables(void* d_tab, uint32_t form, uint32_t k, const uint6
                              const uint64_t* shift, uint32_t direction, hipStream_t s);
 hipError_t launch_ntt(const uint64_t* d_in, uint64_t in_rows, uint64_t in_len, uint32_t n_cols,
                       uint32_t k, uint32_t form, uint32_t direction, bool shift_is_one, uint64_t* d_out,
-                      uint64_t out_rows, const void* d_tab, int* sticky, hipStream_t s);
+                      uint64_t out_rows, const void* d_tab, int* sticky, hipStream_t s,
+                      const uint32_t* plan = nullptr);
+void ntt_plan_of(uint32_t k, uint32_t* out);
 size_t quot_xtab_bytes(uint32_t ext_k);  // b2f_quotient.hip
 size_t quot_consts_bytes();
 hipError_t launch_quot_xtab(void* d_tab, uint32_t form, uint32_t ext_k, const uint64_t* omega,
@@ -2074,9 +2076,49 @@ int quot_consts(b2f_ctx* ctx) {
   if (!ctx->d_quot_consts) HIPCHK(ctx, hipMalloc(&ctx->d_quot_consts, quot_consts_bytes()));
   return B2F_OK;
 }
+
+#ifdef B2F_DIAG
+// Diagnostics build only: B2F_DIAG_NTT_PLAN=l1,l2[,l3[,l4]] read at the call replaces the pass plan
+// of b2f_ntt_columns_dev (tests/test_gpu_ntt_plans.py: plans the product never picks at small k).
+// Returns 0 when the variable is unset (the product plan), 1 with plan = {P, l[0..3]} when it
+// holds a plan the pass kernel can run at this k (k > 10, 2..4 digits, each 1..8, summing to k:
+// every tile then holds 2^(10 - l) >= 4 whole transforms and every row index stays below 2^k),
+// -1 for anything else. There is no fallback: the caller refuses the call on -1.
+int diag_ntt_plan(uint32_t k, uint32_t* plan) {
+  const char* v = getenv("B2F_DIAG_NTT_PLAN");
+  if (!v) return 0;
+  uint32_t P = 0, sum = 0;
+  for (uint32_t d = 0; d < 5; d++) plan[d] = 0;
+  for (const char* c = v;;) {
+    if (P == 4 || *c < '1' || *c > '8') return -1;  // one decimal digit per pass
+    plan[1 + P] = (uint32_t)(*c - '0');
+    sum += plan[1 + P];
+    P++;
+    c++;
+    if (!*c) break;
+    if (*c != ',') return -1;
+    c++;
+  }
+  if (k <= 10 || P < 2 || sum != k) return -1;
+  plan[0] = P;
+  return 1;
+}
+#endif
 }  // namespace
 
 extern "C" {
+
+#ifdef B2F_DIAG
+// Host only: the pass plan b2f_ntt_columns_dev would run a 2^k transform with under the current
+// environment, out = {P, l[0..3]}; B2F_ERR_ARG where it would refuse the call.
+B2F_API int b2f_debug_ntt_plan(uint32_t k, uint32_t* out) {
+  if (!out || k < 1 || k > 28) return B2F_ERR_ARG;
+  const int forced = diag_ntt_plan(k, out);
+  if (forced < 0) return B2F_ERR_ARG;
+  if (!forced) ntt_plan_of(k, out);
+  return B2F_OK;
+}
+#endif
 
 B2F_API int b2f_lagrange_selectors_dev(b2f_ctx* ctx, uint32_t k, uint64_t usable_rows, uint32_t form,
                                        uint64_t* d_out, uint64_t out_rows, void* stream) {
@@ -2224,6 +2266,13 @@ B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_
   const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (uint64_t)n_cols * in_rows * 32;
   const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (uint64_t)n_cols * out_rows * 32;
   if (i0 < o1 && o0 < i1) return set_err(ctx, B2F_ERR_ARG, "ntt: input and output overlap (no in-place transform)");
+  const uint32_t* plan = nullptr;
+#ifdef B2F_DIAG
+  uint32_t forced[5];
+  const int have_plan = diag_ntt_plan(k, forced);
+  if (have_plan < 0) return set_err(ctx, B2F_ERR_ARG, "ntt: the forced pass plan does not fit k = %u", k);
+  if (have_plan) plan = forced;
+#endif
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // the table block of this domain: cached, or built into the next slot
@@ -2256,7 +2305,7 @@ B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_
   }
   const bool shift_is_one = shift[0] == 1 && !(shift[1] | shift[2] | shift[3]);
   HIPCHK(ctx, launch_ntt(d_in, in_rows, in_len, n_cols, k, form, direction, shift_is_one, d_out, out_rows,
-                         tab->d, ctx->d_status + 2, s));
+                         tab->d, ctx->d_status + 2, s, plan));
   timed_end(ctx, tk, s);
   return B2F_OK;
 }

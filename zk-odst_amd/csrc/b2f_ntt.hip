@@ -345,6 +345,9 @@ void ntt_plan(uint32_t k, uint32_t* P, uint32_t* l) {
 
 }  // namespace
 
+// The plan a k gets (host): out = {P, l[0..3]}.
+void ntt_plan_of(uint32_t k, uint32_t* out) { ntt_plan(k, out, out + 1); }
+
 size_t ntt_table_bytes(uint32_t k) {
   const uint32_t h0 = ntt_h0(k);
   return 32ull * (NT_T0_OFF + 2ull * ((1ull << h0) + (1ull << (k - h0))));
@@ -374,7 +377,8 @@ hipError_t launch_ntt_tables(void* d_tab, uint32_t form, uint32_t k, const uint6
 
 hipError_t launch_ntt(const uint64_t* d_in, uint64_t in_rows, uint64_t in_len, uint32_t n_cols,
                       uint32_t k, uint32_t form, uint32_t direction, bool shift_is_one, uint64_t* d_out,
-                      uint64_t out_rows, const void* d_tab, int* sticky, hipStream_t s) {
+                      uint64_t out_rows, const void* d_tab, int* sticky, hipStream_t s,
+                      const uint32_t* plan) {
   NttPass a;
   a.src = d_in;
   a.dst = d_out;
@@ -385,7 +389,14 @@ hipError_t launch_ntt(const uint64_t* d_in, uint64_t in_rows, uint64_t in_len, u
   a.sticky = sticky;
   a.k = k;
   a.n_cols = n_cols;
-  ntt_plan(k, &a.P, a.l);
+  // plan: {P, l[0..3]} in place of ntt_plan's (diagnostics library only, checked by its caller:
+  // k > 10, 2 <= P <= 4, every l[d] in 1..8, their sum k); null from every product caller
+  if (plan) {
+    a.P = plan[0];
+    for (uint32_t d = 0; d < NT_MAXP; d++) a.l[d] = d < plan[0] ? plan[1 + d] : 0u;
+  } else {
+    ntt_plan(k, &a.P, a.l);
+  }
   a.h0 = ntt_h0(k);
   a.mlog = k < NT_LOG ? k : NT_LOG;
   a.prescale = direction == B2F_NTT_FORWARD && !shift_is_one;
