@@ -240,6 +240,17 @@ B2F_API int b2f_export_fp_dev(b2f_ctx* ctx, const uint32_t* d_advice, uint64_t t
                               uint64_t row_begin, uint64_t nrows, uint32_t form,
                               uint64_t* d_out, uint64_t out_rows, void* stream);
 
+/* The fixed column as the prover's fixed columns (keygen data): the trace keeps the sixteen
+ * selectors and k_0 packed in one u32 per row (mask | k_0 << 16, docs/LAYOUT.md §2); this writes
+ * B2F_NUM_FIXED_FP = 17 field columns of rows [row_begin, row_begin + nrows) to
+ * d_out[(c * out_rows + r) * 4 + limb]: c = 0..15 selector bit c as the field's 0 or 1, c = 16
+ * k_0 = q >> 16. `form` is any B2F_FP_*; rows past nrows are not written; arguments, alignment
+ * and errors as b2f_export_fp_dev (nrows < 2^38). One B2F_KERNEL_EXPORT region. Asynchronous. */
+#define B2F_NUM_FIXED_FP 17
+B2F_API int b2f_export_fixed_fp_dev(b2f_ctx* ctx, const uint32_t* d_fixed, uint64_t total_rows,
+                                    uint64_t row_begin, uint64_t nrows, uint32_t form,
+                                    uint64_t* d_out, uint64_t out_rows, void* stream);
+
 /* The spread table as the prover's table columns (SpreadTableChip::load, spread_table.rs:470-508;
  * rows from SpreadTableConfig::generate, spread_table.rs:574-600): column c = 0 tag, 1 dense,
  * 2 spread, row x < 2^16 holds (tag(x), x, spread(x)), rows 2^16 .. usable_rows - 1 the
@@ -389,11 +400,11 @@ B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_
                                 uint32_t direction, uint32_t form, uint64_t* d_out,
                                 uint64_t out_rows, void* stream);
 
-/* The permutation and lookup terms of the quotient numerator on the extended coset, and the
- * division by the vanishing polynomial (halo2_proofs 0.3.0 plonk/permutation/prover.rs and
- * plonk/lookup/prover.rs Committed::construct, EvaluationDomain::divide_by_vanishing_poly). The
- * custom-gate terms are not here: the term calls fold into a caller-supplied accumulator in
- * halo2's order (gates, then the permutation, then each lookup), so a gate pass composes with them.
+/* The custom-gate, permutation and lookup terms of the quotient numerator on the extended coset,
+ * and the division by the vanishing polynomial (the gates of docs/LAYOUT.md §4; halo2_proofs
+ * 0.3.0 plonk/permutation/prover.rs and plonk/lookup/prover.rs Committed::construct,
+ * EvaluationDomain::divide_by_vanishing_poly). The term calls fold into a caller-supplied
+ * accumulator; halo2's order is the gates, then the permutation, then each lookup.
  * Shared conventions: columns are d[(c * rows + i) * 4 + limb] in `form` (any B2F_FP_*; the
  * canonical forms convert at load and store, inputs reduced); n = 2^k, n_ext = 2^ext_k,
  * 1 <= k < ext_k <= 28, rot = 2^(ext_k - k); extended row i is the point X_i = shift omega_ext^i
@@ -413,6 +424,41 @@ B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_
  * not touched. Two b2f_ntt_columns_dev calls take them to the coset like any other column. */
 B2F_API int b2f_lagrange_selectors_dev(b2f_ctx* ctx, uint32_t k, uint64_t usable_rows, uint32_t form,
                                        uint64_t* d_out, uint64_t out_rows, void* stream);
+
+/* Custom-gate terms. d_advice: the ten advice columns in halo2 order (the block
+ * b2f_export_fp_dev writes, extended); d_fixed: the seventeen columns of b2f_export_fixed_fp_dev,
+ * extended; both with stride rows >= n_ext. x@j of extended row i is row (i + j rot) mod n_ext
+ * (a true mod: 11 rot may exceed n_ext). Each term is q_g p with q_g fixed column g; T = 74, in
+ * ascending selector bit g, within a gate in the order of docs/LAYOUT.md §4 with "for all k"
+ * expanded k = 0..3 outermost (a_i = advice column b2f_halo2_column_index(i), k_0 = fixed
+ * column 16; docs/LAYOUT.md §4.1 has the same list):
+ *   0  (2)  a_7@0 - a_1@0 - 2^16 a_1@1;  a_8@0 - a_1@2 - 2^16 a_1@3
+ *   1  (8)  per k, k1 = (k+1)&3, k2 = (k+2)&3:  a_7@3k - a_1@(3k1+1) - 2^8 a_1@3k2;
+ *           a_8@3k - a_2@(3k1+1) - 2^16 a_2@3k2
+ *   2  (8)  per k, k3 = (k+3)&3:  a_7@2k - a_6@2k3 - 2 a_1@2k;  a_8@2k - a_6@2k3 - 4 a_2@2k
+ *   3  (2)  sum_k 2^16k (a_3@k + a_4@k + a_5@k - a_1@k) - 2^64 a_9@0;  a_9@0 (a_9@0 - 1)(a_9@0 - 2)
+ *   4  (12) per k:  a_3@3k + a_4@3k - a_2@3k - 2^16 a_2@(3k+1) - 2 a_2@(3k+2);  a_0@3k;  a_0@(3k+1)
+ *   5  (2)  sum_k 2^16k (a_3@k + a_4@k - a_1@k) - 2^64 a_9@0;  a_9@0 (a_9@0 - 1)
+ *   6  (4)  per k:  a_3@2k + a_4@2k - a_2@2k - 2 a_2@(2k+1)
+ *   7  (2)  as 3
+ *   8  (12) per k:  a_3@2k + a_4@2k - a_2@2k - 2^30 a_6@2k - 2 a_2@(2k+1);  a_0@2k (a_0@2k - 1);
+ *           a_6@2k (a_6@2k - 1)
+ *   9  (2)  as 5
+ *   10 (4)  as 6
+ *   11 (2)  a_7@0 - a_1@0 - 2^16 a_1@2;  a_8@0 - a_1@4 - 2^16 a_1@6
+ *   12 (4)  as 6
+ *   13 (4)  per k:  a_3@2k + a_4@2k + a_5@2k - a_2@2k - 2 a_2@(2k+1)
+ *   14 (1)  a_1@0 - k_0@0
+ *   15 (5)  a_5@0 (a_5@0 - 1);  per k:  a_1@k - 65535 a_5@0
+ * Gates with the same polynomials are separate terms. The largest degree is 4 (bit 3 with its
+ * selector), the lookup's, so ext_k = k + 2 serves all three term calls. No omega and no shift:
+ * the gates never use X_i. halo2's keygen would combine simple selectors into fewer fixed
+ * columns; that is not modelled. Errors, nothing launched: B2F_ERR_ARG for a null or misaligned
+ * pointer, k or ext_k out of range, form > 3, y >= p, a forbidden overlap; B2F_ERR_ROWS for
+ * rows < n_ext. */
+B2F_API int b2f_quotient_gates_dev(b2f_ctx* ctx, uint32_t k, uint32_t ext_k, const uint64_t* d_advice,
+                                   const uint64_t* d_fixed, uint64_t rows, const uint64_t y[4],
+                                   const uint64_t* d_h_in, uint64_t* d_h_out, uint32_t form, void* stream);
 
 /* Permutation terms. All blocks are on the extended coset with stride rows >= n_ext: d_l the
  * three selector columns; d_advice the ten advice columns in halo2 order, the block

@@ -1,5 +1,5 @@
-"""Throughput of the quotient calls (b2f_quotient_permutation_dev, b2f_quotient_lookup_dev,
-b2f_quotient_divide_dev) at k = 17, ext_k = 19: both fields, Montgomery form, chunk_len 2 and 3,
+"""Throughput of the quotient calls (b2f_quotient_gates_dev, b2f_quotient_permutation_dev,
+b2f_quotient_lookup_dev, b2f_quotient_divide_dev) at k = 17, ext_k = 19: both fields, Montgomery form, chunk_len 2 and 3,
 HIP-event times (b2f_kernel_times) of repeated calls with a warm X_i table. One JSON line per
 (call, field, chunk_len) with the bytes the call must move, the resulting GB/s and two floors
 measured in the same process:
@@ -15,6 +15,10 @@ of columns already counted: not counted again), h_in and h_out. Products per row
   permutation  4 per column (32) + per set: the l_active product, a fold, and from the second set on
                the link product and its fold + 3 for e_0, e_1 + 2 folds + X_i + the final y^sets
   lookup       12 in the terms + 5 folds
+  gates        118, counted from quot_gates_kernel: 28 by the weights 2^8, 2^16, 2^30, 2^64 and
+               65535, 11 in the carry and boolean polynomials, 50 Horner steps in y inside the
+               gates, 16 selector products q_g y^S_g, 12 products of a gate's polynomial sum by
+               its selector(s), 1 for y^74 h_in
   divide       1
 For scale, `ntt_ms` is the coeff_to_extended NTT (b2f_ntt_columns_dev, k = 19, in_len = 2^17) of
 the same columns the call reads, from the same run."""
@@ -67,6 +71,9 @@ def copy_ms(torch, nbytes, reps=7):
 def permutation_products(chunk_len):
     sets = -(-8 // chunk_len)
     return 32 + 2 * sets + 2 * (sets - 1) + 3 + 2 + 1 + 1
+
+
+GATES_PRODUCTS = 28 + 11 + 50 + 16 + 12 + 1
 
 
 def main():
@@ -164,6 +171,10 @@ def main():
             del z
         st = measure(lambda: eng.quotient_lookup(k, ext_k, l, lk, beta, gamma, y, h=h, form=form))
         record("lookup", 0, 3 + 5, 17, st)
+        fx = rand(_lib.NUM_FIXED_FP, n_ext)
+        st = measure(lambda: eng.quotient_gates(k, ext_k, adv, fx, y, h=h, form=form))
+        record("gates", 0, 10 + _lib.NUM_FIXED_FP, GATES_PRODUCTS, st)
+        del fx
         st = measure(lambda: eng.quotient_divide(k, ext_k, zeta, h, form=form))
         record("divide", 0, 0, 1, st)
         del l, adv, sigma, lk, h, coeff

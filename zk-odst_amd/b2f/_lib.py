@@ -19,6 +19,7 @@ HEADER = os.path.join(os.path.dirname(PKG_ROOT), "include", "b2f.h")
 
 NUM_ADVICE = 10
 NUM_GATES = 16
+NUM_FIXED_FP = 17  # B2F_NUM_FIXED_FP: the sixteen selectors and k_0 as field columns
 CODE_LOOKUP = 16
 CODE_COPY = 17
 CODE_FIXED = 18
@@ -103,6 +104,7 @@ SIGNATURES = [
     ("b2f_copy_constraints", U64, [ctypes.c_uint32, P, U64]),
     ("b2f_chain_inputs_dev", I32, [P, P, P, P, P, ctypes.c_uint32, SIZE, P, P]),
     ("b2f_export_fp_dev", I32, [P, P, U64, U64, U64, ctypes.c_uint32, P, U64, P]),
+    ("b2f_export_fixed_fp_dev", I32, [P, P, U64, U64, U64, ctypes.c_uint32, P, U64, P]),
     ("b2f_lookup_columns_dev", I32, [P, P, U64, P, ctypes.c_uint32, U64, P, P, P,
                                      ctypes.c_uint32, P, U64, P, P]),
     ("b2f_spread_table_dev", I32, [P, U64, ctypes.c_uint32, P, U64, P]),
@@ -116,6 +118,8 @@ SIGNATURES = [
     ("b2f_ntt_columns_dev", I32, [P, P, U64, U64, ctypes.c_uint32, ctypes.c_uint32, P, P,
                                   ctypes.c_uint32, ctypes.c_uint32, P, U64, P]),
     ("b2f_lagrange_selectors_dev", I32, [P, ctypes.c_uint32, U64, ctypes.c_uint32, P, U64, P]),
+    ("b2f_quotient_gates_dev", I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, P, U64, P, P, P,
+                                     ctypes.c_uint32, P]),
     ("b2f_quotient_permutation_dev", I32, [P, ctypes.c_uint32, ctypes.c_uint32, U64, P, P, P, P,
                                            ctypes.c_uint32, U64, P, P, P, P, P, P, P, P,
                                            ctypes.c_uint32, P]),

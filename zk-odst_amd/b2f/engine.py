@@ -144,6 +144,12 @@ class Engine:
                                                int(row_begin), int(nrows), int(form),
                                                _vp(d_out), int(out_rows), _vp(stream)))
 
+    def export_fixed_fp_dev(self, d_fixed, total_rows, row_begin, nrows, form, d_out, out_rows,
+                            stream=0):
+        self._check(self.lib.b2f_export_fixed_fp_dev(self.ctx, _vp(d_fixed), int(total_rows),
+                                                     int(row_begin), int(nrows), int(form),
+                                                     _vp(d_out), int(out_rows), _vp(stream)))
+
     def lookup_columns_dev(self, d_adv, total_rows, d_row_begin, n_circuits, usable_rows, theta,
                            beta, gamma, form, d_out, out_rows, d_first_bad, stream=0):
         """b2f_lookup_columns_dev; theta/beta/gamma are Python ints (canonical Fp)."""
@@ -252,6 +258,14 @@ class Engine:
         self._check(self.lib.b2f_lagrange_selectors_dev(self.ctx, int(k), int(usable_rows), int(form),
                                                         _vp(d_out), int(out_rows), _vp(stream)))
 
+    def quotient_gates_dev(self, k, ext_k, d_advice, d_fixed, rows, y, d_h_in, d_h_out, form, stream=0):
+        """b2f_quotient_gates_dev; y is a Python int (canonical), d_h_in 0 or None for a zero
+        accumulator."""
+        lim = self._limbs(y)
+        self._check(self.lib.b2f_quotient_gates_dev(
+            self.ctx, int(k), int(ext_k), _vp(d_advice), _vp(d_fixed), int(rows), lim[0],
+            _vp(d_h_in) if d_h_in else None, _vp(d_h_out), int(form), _vp(stream)))
+
     def quotient_permutation_dev(self, k, ext_k, usable_rows, d_l, d_advice, d_sigma, d_z, chunk_len,
                                  rows, omega_ext, shift, delta, beta, gamma, y, d_h_in, d_h_out, form,
                                  stream=0):
@@ -310,6 +324,30 @@ class Engine:
         inverse NTT with shift 1, then the forward one on the coset with in_len = 2^k."""
         coeff = self.ntt_columns(cols, k, inverse=True, form=form, stream=stream)
         return self.ntt_columns(coeff, ext_k, shift=shift, in_len=1 << int(k), form=form, stream=stream)
+
+    def quotient_gates(self, k, ext_k, advice, fixed, y, h=None, out=None, form=_lib.FP_MONTGOMERY,
+                       stream=None):
+        """The 74 custom-gate terms folded into h (b2f_quotient_gates_dev). advice [10, rows, 4]
+        (halo2 column order, as export_fp writes them) and fixed [17, rows, 4] (as export_fixed_fp
+        writes them): extended-coset columns of one stride rows >= 2^ext_k, int64 in `form`; h and
+        out as in quotient_permutation. The gates come first in halo2's order: start h here."""
+        import torch
+
+        rows = int(advice.shape[1]) if advice.dim() == 3 else 0
+        for name, t, nc in (("advice", advice, _lib.NUM_ADVICE), ("fixed", fixed, _lib.NUM_FIXED_FP)):
+            self._cols("quotient_gates: " + name, t, nc, 1 << int(ext_k))
+            if int(t.shape[1]) != rows:
+                raise _lib.B2FError(_lib.ERR_ARG, "quotient_gates: the blocks must share one stride")
+        if h is not None:
+            self._h("quotient_gates: h", h, ext_k)
+        if out is None:
+            out = h if h is not None else torch.empty((1 << int(ext_k), 4), dtype=torch.int64,
+                                                      device=advice.device)
+        self._h("quotient_gates: out", out, ext_k)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.quotient_gates_dev(k, ext_k, advice.data_ptr(), fixed.data_ptr(), rows, y,
+                                h.data_ptr() if h is not None else 0, out.data_ptr(), form, s)
+        return out
 
     def quotient_permutation(self, k, ext_k, usable_rows, l, advice, sigma, z, chunk_len, shift, beta,
                              gamma, y, h=None, out=None, form=_lib.FP_MONTGOMERY, stream=None):
@@ -502,6 +540,25 @@ class DeviceBatch:
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         eng.export_fp_dev(self.advice.data_ptr(), self.total_rows, row_begin, nrows, form,
                           out.data_ptr(), out.shape[1], s)
+        return out
+
+    def export_fixed_fp(self, eng, row_begin=0, nrows=None, form=_lib.FP_MONTGOMERY, out=None,
+                        stream=None):
+        """Fixed rows [row_begin, row_begin + nrows) as the prover's fixed columns: int64 tensor
+        [17 (selector bits 0..15, then k_0), out_rows, 4] of field elements in `form`
+        (b2f_export_fixed_fp_dev). `out` may be a preallocated tensor of that shape (out_rows >=
+        nrows; rows past nrows are left as they are)."""
+        torch = self.torch
+        nrows = self.total_rows - row_begin if nrows is None else int(nrows)
+        if out is None:
+            out = torch.empty((_lib.NUM_FIXED_FP, nrows, 4), dtype=torch.int64,
+                              device=self.fixed.device)
+        if out.dim() != 3 or out.shape[0] != _lib.NUM_FIXED_FP or out.shape[2] != 4 \
+                or out.dtype != torch.int64 or not out.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "export_fixed_fp: out must be contiguous int64 [17, rows, 4]")
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        eng.export_fixed_fp_dev(self.fixed.data_ptr(), self.total_rows, row_begin, nrows, form,
+                                out.data_ptr(), out.shape[1], s)
         return out
 
     def lookup_columns(self, eng, row_begin, usable_rows, theta, beta, gamma,

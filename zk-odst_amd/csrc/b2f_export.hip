@@ -35,6 +35,8 @@ hipError_t launch_export_fp(const uint32_t* d_advice, uint64_t total_rows, uint6
                             int cu_count, unsigned* tctr, hipStream_t s);
 hipError_t launch_spread_table(uint64_t usable_rows, uint32_t form, uint64_t* d_out,
                                uint64_t out_rows, hipStream_t s);
+hipError_t launch_export_fixed_fp(const uint32_t* d_fixed, uint64_t row_begin, uint64_t nrows,
+                                  uint32_t form, uint64_t* d_out, uint64_t out_rows, hipStream_t s);
 
 namespace {
 
@@ -208,7 +210,42 @@ __global__ __launch_bounds__(256) void spread_table_kernel(uint64_t usable_rows,
   }
 }
 
+// The packed fixed column (mask | k_0 << 16, docs/LAYOUT.md §2) as the prover's seventeen fixed
+// columns: c < 16 selector bit c as the field's 0 or 1, c = 16 the constant k_0. Two lanes per row,
+// as the export kernel: one 4-byte read and seventeen 16-byte stores per lane, each store
+// instruction of a wave 1 KiB contiguous. The field's 1 and k_0 are formed once per lane.
+template <int FORM>
+__global__ __launch_bounds__(256) void export_fixed_fp_kernel(const uint32_t* __restrict__ fixed,
+                                                              uint64_t row_begin, uint64_t nrows,
+                                                              uint64_t* __restrict__ out,
+                                                              uint64_t out_rows) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t row = i >> 1;
+  const uint32_t half = (uint32_t)(i & 1);
+  if (row >= nrows) return;
+  const uint32_t q = fixed[row_begin + row];
+  const u64x2 zero = u64x2{0, 0}, one = fp_half<FORM>(1u, half), k0 = fp_half<FORM>(q >> 16, half);
+#pragma unroll
+  for (int c = 0; c < B2F_NUM_FIXED_FP; c++) {
+    u64x2* dst = reinterpret_cast<u64x2*>(out + (uint64_t)c * out_rows * 4);
+    const u64x2 e = c == 16 ? k0 : ((q >> c) & 1u ? one : zero);
+    __builtin_nontemporal_store(e, dst + 2 * row + half);
+  }
+}
+
 }  // namespace
+
+hipError_t launch_export_fixed_fp(const uint32_t* d_fixed, uint64_t row_begin, uint64_t nrows,
+                                  uint32_t form, uint64_t* d_out, uint64_t out_rows, hipStream_t s) {
+  const dim3 grid((uint32_t)((2 * nrows + 255) / 256)), block(256);
+  if (form == B2F_FP_BN254_MONTGOMERY)
+    hipLaunchKernelGGL(export_fixed_fp_kernel<3>, grid, block, 0, s, d_fixed, row_begin, nrows, d_out, out_rows);
+  else if (form & 1u)
+    hipLaunchKernelGGL(export_fixed_fp_kernel<1>, grid, block, 0, s, d_fixed, row_begin, nrows, d_out, out_rows);
+  else
+    hipLaunchKernelGGL(export_fixed_fp_kernel<0>, grid, block, 0, s, d_fixed, row_begin, nrows, d_out, out_rows);
+  return hipGetLastError();
+}
 
 hipError_t launch_spread_table(uint64_t usable_rows, uint32_t form, uint64_t* d_out,
                                uint64_t out_rows, hipStream_t s) {

@@ -89,6 +89,9 @@ hipError_t launch_quot_lookup(uint32_t k, uint32_t ext_k, const uint64_t* d_l, c
                               uint64_t rows, const uint64_t* beta, const uint64_t* gamma, const uint64_t* y,
                               const uint64_t* d_h_in, uint64_t* d_h_out, uint32_t form, void* d_consts,
                               hipStream_t s);
+hipError_t launch_quot_gates(uint32_t k, uint32_t ext_k, const uint64_t* d_advice, const uint64_t* d_fixed,
+                             uint64_t rows, const uint64_t* y, const uint64_t* d_h_in, uint64_t* d_h_out,
+                             uint32_t form, void* d_consts, hipStream_t s);
 size_t quot_divisor_bytes(uint32_t k, uint32_t ext_k);
 hipError_t launch_quot_divisors(void* d_dtab, uint32_t form, uint32_t k, uint32_t ext_k, const uint64_t* omega,
                                 const uint64_t* shift, hipStream_t s);
@@ -97,6 +100,8 @@ hipError_t launch_quot_divide(uint32_t k, uint32_t ext_k, const uint64_t* d_h_in
 hipError_t launch_export_fp(const uint32_t* d_advice, uint64_t total_rows, uint64_t row_begin,
                             uint64_t nrows, uint32_t form, uint64_t* d_out, uint64_t out_rows,
                             int cu_count, unsigned* tctr, hipStream_t s);  // b2f_export.hip
+hipError_t launch_export_fixed_fp(const uint32_t* d_fixed, uint64_t row_begin, uint64_t nrows,
+                                  uint32_t form, uint64_t* d_out, uint64_t out_rows, hipStream_t s);
 size_t fused_scratch_bytes(uint64_t tiles);
 uint64_t fused_instance_tiles(uint64_t total_rows, uint64_t n);
 hipError_t launch_eval_fast(const uint32_t* d_adv, const uint32_t* d_fixed, const uint64_t* d_off, uint32_t n,
@@ -1655,6 +1660,28 @@ B2F_API int b2f_export_fp_dev(b2f_ctx* ctx, const uint32_t* d_advice, uint64_t t
   return B2F_OK;
 }
 
+B2F_API int b2f_export_fixed_fp_dev(b2f_ctx* ctx, const uint32_t* d_fixed, uint64_t total_rows,
+                                    uint64_t row_begin, uint64_t nrows, uint32_t form,
+                                    uint64_t* d_out, uint64_t out_rows, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  if (!d_fixed || !d_out) return set_err(ctx, B2F_ERR_ARG, "export fixed: null buffer");
+  if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "export fixed: unknown form %u", form);
+  if ((uintptr_t)d_out & 15) return set_err(ctx, B2F_ERR_ARG, "export fixed: d_out must be 16-byte aligned");
+  if (row_begin > total_rows || nrows > total_rows - row_begin)
+    return set_err(ctx, B2F_ERR_ROWS, "export fixed: rows [%llu, +%llu) exceed total_rows %llu",
+                   (unsigned long long)row_begin, (unsigned long long)nrows,
+                   (unsigned long long)total_rows);
+  if (out_rows < nrows) return set_err(ctx, B2F_ERR_ROWS, "export fixed: out_rows < nrows");
+  if (nrows >= (1ull << 38)) return set_err(ctx, B2F_ERR_ROWS, "export fixed: 2^38 rows or more in one call");
+  if (nrows == 0) return B2F_OK;
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int tk = timed_begin(ctx, B2F_KERNEL_EXPORT, s);
+  HIPCHK(ctx, launch_export_fixed_fp(d_fixed, row_begin, nrows, form, d_out, out_rows, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
 B2F_API int b2f_lookup_columns_dev(b2f_ctx* ctx, const uint32_t* d_advice, uint64_t total_rows,
                                    const uint64_t* d_row_begin, uint32_t n_circuits,
                                    uint64_t usable_rows, const uint64_t theta[4],
@@ -2135,6 +2162,30 @@ B2F_API int b2f_lagrange_selectors_dev(b2f_ctx* ctx, uint32_t k, uint64_t usable
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
   HIPCHK(ctx, launch_lagrange_selectors(k, (uint32_t)usable_rows, form, d_out, out_rows, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API int b2f_quotient_gates_dev(b2f_ctx* ctx, uint32_t k, uint32_t ext_k, const uint64_t* d_advice,
+                                   const uint64_t* d_fixed, uint64_t rows, const uint64_t y[4],
+                                   const uint64_t* d_h_in, uint64_t* d_h_out, uint32_t form, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "quotient gates";
+  if (!d_advice || !d_fixed || !y) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (((uintptr_t)d_advice | (uintptr_t)d_fixed) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "%s: buffers must be 16-byte aligned", what);
+  if (int rc = quot_check_common(ctx, what, k, ext_k, rows, form, d_h_in, d_h_out)) return rc;
+  if (!fe_canonical(form, y)) return set_err(ctx, B2F_ERR_ARG, "%s: y is >= p", what);
+  const uint64_t hb = 32ull << ext_k;
+  if (ranges_overlap(d_h_out, hb, d_advice, B2F_NUM_ADVICE * rows * 32) ||
+      ranges_overlap(d_h_out, hb, d_fixed, B2F_NUM_FIXED_FP * rows * 32))
+    return set_err(ctx, B2F_ERR_ARG, "%s: h_out overlaps an input block", what);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = quot_consts(ctx)) return rc;
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_quot_gates(k, ext_k, d_advice, d_fixed, rows, y, d_h_in, d_h_out, form,
+                                ctx->d_quot_consts, s));
   timed_end(ctx, tk, s);
   return B2F_OK;
 }

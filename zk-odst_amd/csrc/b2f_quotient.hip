@@ -1,6 +1,7 @@
-// b2f_quotient.hip -- the permutation and lookup terms of the quotient numerator on the extended
-// coset and the division by the vanishing polynomial (b2f_lagrange_selectors_dev,
-// b2f_quotient_permutation_dev, b2f_quotient_lookup_dev, b2f_quotient_divide_dev): halo2_proofs
+// b2f_quotient.hip -- the custom-gate, permutation and lookup terms of the quotient numerator on
+// the extended coset and the division by the vanishing polynomial (b2f_lagrange_selectors_dev,
+// b2f_quotient_gates_dev, b2f_quotient_permutation_dev, b2f_quotient_lookup_dev,
+// b2f_quotient_divide_dev): the gates of docs/LAYOUT.md §4 and halo2_proofs
 // 0.3.0 plonk/permutation/prover.rs Committed::construct, plonk/lookup/prover.rs
 // Committed::construct and EvaluationDomain::divide_by_vanishing_poly. DESIGN.md §4.5.
 //
@@ -225,6 +226,193 @@ __global__ __launch_bounds__(QT_THREADS) void quot_lookup_kernel(const QuotLooku
   st<F, MONT>(a.h_out + 4ull * i, h);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The custom-gate terms (b2f_quotient_gates_dev): the 74 polynomials of docs/LAYOUT.md §4, each
+// times its selector column, folded with y in the order of docs/LAYOUT.md §4.1.
+//
+// With m_g polynomials p_g,0 .. p_g,m-1 in gate g and S_g terms after the gate's last one,
+//   h_out = y^74 h_in + sum_g (q_g y^S_g) P_g,   P_g = sum_t y^(m_g - 1 - t) p_g,t  (Horner in y),
+// so a gate costs m_g - 1 Horner products, one for its selector and one for P_g instead of 2 m_g,
+// the gates may be visited in any order, and gates with the same polynomials (3/7, 5/9, 6/10/12)
+// share P_g: (q_3 y^S_3 + q_7 y^S_7) P_3. The XOR limb sum X_k = a_3 + a_4 - a_2 - 2 a_2@+1 is
+// formed once per k for bits 6/10/12, 8 and 13, the dense sum of the ADD blocks once for bits
+// 3/7 and 5/9. The weights and the powers of y are Montgomery constants written by a one-lane
+// kernel (GateConsts); 2 a and 4 a are doublings.
+//
+// A thread streams gate by gate: at most three Horner accumulators and one X_k are live next to
+// the row's accumulator, never the 67 advice cells of the row. Rotated reads are other rows of the
+// same columns, (i + j rot) mod n_ext with n_ext a power of two (a mask: exact even where 11 rot
+// exceeds n_ext); lanes sit on adjacent rows, so every one is as coalesced as the rotation-0 read.
+// The re-reads (a row's cells are read by up to 12 rows, all within 11 rot rows) are left to the
+// caches; the tile order below keeps neighbouring tiles on one L2. DESIGN.md §4.5.
+
+// halo2 column of a_i (b2f_halo2_column_index)
+constexpr uint32_t GA0 = 7, GA1 = 8, GA2 = 9, GA3 = 1, GA4 = 2, GA5 = 0, GA6 = 3, GA7 = 4, GA8 = 5, GA9 = 6;
+constexpr uint32_t QG_TERMS = 74;
+constexpr uint32_t QG_COUNT[16] = {2, 8, 8, 2, 12, 2, 4, 2, 12, 2, 4, 2, 4, 4, 1, 5};
+
+struct GateConsts {
+  Fe y, yt;      // y, y^74
+  Fe ys[16];     // y^S_g, S_g = the number of terms after gate g's last one
+  Fe w8, w16, w30, w64, w65535;
+};
+
+template <class F>
+__global__ void quot_gate_consts_kernel(GateConsts* c, Words4 y) {
+  if (blockIdx.x || threadIdx.x) return;
+  const Fe yy = to_mont<F>(load_words(y.v));
+  c->y = yy;
+  c->yt = fe_pow<F>(yy, QG_TERMS);
+  uint32_t after = QG_TERMS;
+  for (int g = 0; g < 16; g++) {
+    after -= QG_COUNT[g];
+    c->ys[g] = fe_pow<F>(yy, after);
+  }
+  const Fe w16 = from_u32<F>(1u << 16), w32 = mul<F>(w16, w16);
+  c->w8 = from_u32<F>(1u << 8);
+  c->w16 = w16;
+  c->w30 = from_u32<F>(1u << 30);
+  c->w64 = mul<F>(w32, w32);
+  c->w65535 = from_u32<F>(65535u);
+}
+
+struct QuotGates {
+  const uint64_t *adv, *fix, *h_in;
+  uint64_t* h_out;
+  const GateConsts* c;
+  uint64_t rows;
+  uint32_t ext_k, rot;
+};
+
+template <class F, bool MONT>
+__global__ __launch_bounds__(QT_THREADS, 2) void quot_gates_kernel(const QuotGates a) {
+  // Workgroups b and b + 8 share an L2: deal each of the eight a run of consecutive tiles, so the
+  // 11 rot halo rows a tile shares with the next one are fetched into one L2, not two.
+  uint32_t tile = blockIdx.x;
+  if (!(gridDim.x & 7u)) tile = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const uint32_t i = tile * QT_THREADS + threadIdx.x;
+  const uint32_t mask = (1u << a.ext_k) - 1u;
+  if (i > mask) return;
+  const GateConsts& c = *a.c;
+  // `row` is i behind an opaque copy renewed at every step: the 84 element addresses of a row
+  // are otherwise all formed up front and held (two VGPRs each) until their loads
+  uint32_t row = i;
+  auto step = [&]() {
+    __builtin_amdgcn_sched_barrier(0);
+    row = i;
+    asm volatile("" : "+v"(row));
+  };
+  auto A = [&](uint32_t col, uint32_t j) {
+    return ld<F, MONT>(a.adv + 4ull * (col * a.rows + ((row + j * a.rot) & mask)));
+  };
+  auto Q = [&](uint32_t g) { return ld<F, MONT>(a.fix + 4ull * (g * a.rows + row)); };
+  auto dbl = [](const Fe& x) { return add<F>(x, x); };
+  auto horner = [&](const Fe& P, const Fe& t) { return add<F>(mul<F>(P, c.y), t); };
+  auto sel = [&](uint32_t g) { return mul<F>(Q(g), c.ys[g]); };
+
+  Fe acc = a.h_in ? mul<F>(ld<F, MONT>(a.h_in + 4ull * i), c.yt) : fe_zero();
+
+  {  // bits 0 and 11: the two 32-bit halves of a word from its dense limbs
+    const Fe a7 = A(GA7, 0), a8 = A(GA8, 0), d0 = A(GA1, 0), d2 = A(GA1, 2);
+    Fe P = sub<F>(sub<F>(a7, d0), mul<F>(c.w16, A(GA1, 1)));
+    P = horner(P, sub<F>(sub<F>(a8, d2), mul<F>(c.w16, A(GA1, 3))));
+    acc = add<F>(acc, mul<F>(sel(0), P));
+    P = sub<F>(sub<F>(a7, d0), mul<F>(c.w16, d2));
+    P = horner(P, sub<F>(sub<F>(a8, A(GA1, 4)), mul<F>(c.w16, A(GA1, 6))));
+    acc = add<F>(acc, mul<F>(sel(11), P));
+    // bit 14: the constant
+    acc = add<F>(acc, mul<F>(sel(14), sub<F>(d0, Q(16))));
+  }
+  step();
+  {  // bit 15: the f mask
+    const Fe f = A(GA5, 0), m = mul<F>(c.w65535, f);
+    Fe P = mul<F>(f, sub<F>(f, one<F>()));
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) P = horner(P, sub<F>(A(GA1, k), m));
+    acc = add<F>(acc, mul<F>(sel(15), P));
+  }
+  step();
+  {  // bits 3/7 (ADD3) and 5/9 (ADD2): the dense sums, then the carry polynomials
+    Fe S2 = fe_zero(), M = fe_zero();
+#pragma unroll
+    for (int k = 3; k >= 0; k--) {
+      const Fe d = sub<F>(add<F>(A(GA3, k), A(GA4, k)), A(GA1, k));
+      const Fe m = A(GA5, k);
+      S2 = k == 3 ? d : add<F>(mul<F>(S2, c.w16), d);
+      M = k == 3 ? m : add<F>(mul<F>(M, c.w16), m);
+      step();
+    }
+    const Fe c9 = A(GA9, 0);
+    S2 = sub<F>(S2, mul<F>(c.w64, c9));
+    const Fe C2 = mul<F>(c9, sub<F>(c9, one<F>()));
+    const Fe C3 = mul<F>(C2, sub<F>(c9, dbl(one<F>())));
+    acc = add<F>(acc, mul<F>(add<F>(sel(5), sel(9)), horner(S2, C2)));
+    acc = add<F>(acc, mul<F>(add<F>(sel(3), sel(7)), horner(add<F>(S2, M), C3)));
+  }
+  step();
+  {  // bit 1: the rot-24 recomposition
+    Fe P = fe_zero();
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+      const uint32_t k1 = (k + 1) & 3u, k2 = (k + 2) & 3u;
+      const Fe p0 = sub<F>(sub<F>(A(GA7, 3 * k), A(GA1, 3 * k1 + 1)), mul<F>(c.w8, A(GA1, 3 * k2)));
+      P = k ? horner(P, p0) : p0;
+      P = horner(P, sub<F>(sub<F>(A(GA8, 3 * k), A(GA2, 3 * k1 + 1)), mul<F>(c.w16, A(GA2, 3 * k2))));
+      step();
+    }
+    acc = add<F>(acc, mul<F>(sel(1), P));
+  }
+  step();
+  {  // bit 4: the XOR of the rot-24 block, split 8 + 8
+    Fe P = fe_zero();
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+      Fe x = sub<F>(add<F>(A(GA3, 3 * k), A(GA4, 3 * k)), A(GA2, 3 * k));
+      x = sub<F>(sub<F>(x, mul<F>(c.w16, A(GA2, 3 * k + 1))), dbl(A(GA2, 3 * k + 2)));
+      P = k ? horner(P, x) : x;
+      P = horner(P, A(GA0, 3 * k));
+      P = horner(P, A(GA0, 3 * k + 1));
+      step();
+    }
+    acc = add<F>(acc, mul<F>(sel(4), P));
+  }
+  step();
+  {  // bit 2: the rot-63 recomposition
+    Fe P = fe_zero();
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+      const Fe zb = A(GA6, 2 * ((k + 3) & 3u));
+      const Fe p0 = sub<F>(sub<F>(A(GA7, 2 * k), zb), dbl(A(GA1, 2 * k)));
+      P = k ? horner(P, p0) : p0;
+      P = horner(P, sub<F>(sub<F>(A(GA8, 2 * k), zb), dbl(dbl(A(GA2, 2 * k)))));
+      step();
+    }
+    acc = add<F>(acc, mul<F>(sel(2), P));
+  }
+  step();
+  {  // the 8-row XOR family: bits 6/10/12, 8 (rot-63: split 15 + 1) and 13 (three inputs)
+    Fe P6 = fe_zero(), P8 = fe_zero(), P13 = fe_zero();
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+      Fe x = sub<F>(add<F>(A(GA3, 2 * k), A(GA4, 2 * k)), A(GA2, 2 * k));
+      x = sub<F>(x, dbl(A(GA2, 2 * k + 1)));
+      const Fe x3 = add<F>(x, A(GA5, 2 * k));
+      const Fe zb = A(GA6, 2 * k), tag = A(GA0, 2 * k);
+      const Fe x8 = sub<F>(x, mul<F>(c.w30, zb));
+      P6 = k ? horner(P6, x) : x;
+      P13 = k ? horner(P13, x3) : x3;
+      P8 = k ? horner(P8, x8) : x8;
+      P8 = horner(P8, mul<F>(tag, sub<F>(tag, one<F>())));
+      P8 = horner(P8, mul<F>(zb, sub<F>(zb, one<F>())));
+      step();
+    }
+    acc = add<F>(acc, mul<F>(add<F>(add<F>(sel(6), sel(10)), sel(12)), P6));
+    acc = add<F>(acc, mul<F>(sel(8), P8));
+    acc = add<F>(acc, mul<F>(sel(13), P13));
+  }
+  st<F, MONT>(a.h_out + 4ull * i, acc);
+}
+
 // (X_i^n - 1)^-1 has period rot = 2^(ext_k - k) in i: X_i^n = shift^n (omega^n)^(i mod rot).
 // Divisor block of one (field, k, ext_k, omega, shift), in 32-byte elements: [0] header, word 0 =
 // QT_DIV_FIELD when omega is no primitive root or some divisor is zero (| QT_DIV_CHECK when an
@@ -299,7 +487,8 @@ size_t quot_xtab_bytes(uint32_t ext_k) {
   return 32ull * (QT_T0_OFF + (1ull << h0) + (1ull << (ext_k - h0)));
 }
 
-size_t quot_consts_bytes() { return sizeof(QuotConsts); }
+// one block serves both kinds of term call
+size_t quot_consts_bytes() { return sizeof(QuotConsts) > sizeof(GateConsts) ? sizeof(QuotConsts) : sizeof(GateConsts); }
 
 hipError_t launch_quot_xtab(void* d_tab, uint32_t form, uint32_t ext_k, const uint64_t* omega,
                             const uint64_t* shift, hipStream_t s) {
@@ -394,6 +583,40 @@ hipError_t launch_quot_lookup(uint32_t k, uint32_t ext_k, const uint64_t* d_l, c
       break;
     default:
       hipLaunchKernelGGL((quot_lookup_kernel<Bn254, true>), grid, block, 0, s, a);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_quot_gates(uint32_t k, uint32_t ext_k, const uint64_t* d_advice, const uint64_t* d_fixed,
+                             uint64_t rows, const uint64_t* y, const uint64_t* d_h_in, uint64_t* d_h_out,
+                             uint32_t form, void* d_consts, hipStream_t s) {
+  QuotGates a;
+  a.adv = d_advice;
+  a.fix = d_fixed;
+  a.h_in = d_h_in;
+  a.h_out = d_h_out;
+  a.c = static_cast<const GateConsts*>(d_consts);
+  a.rows = rows;
+  a.ext_k = ext_k;
+  a.rot = 1u << (ext_k - k);
+  GateConsts* c = static_cast<GateConsts*>(d_consts);
+  if ((form >> 1) & 1u)
+    hipLaunchKernelGGL(quot_gate_consts_kernel<Bn254>, dim3(1), dim3(64), 0, s, c, words4(y));
+  else
+    hipLaunchKernelGGL(quot_gate_consts_kernel<Pallas>, dim3(1), dim3(64), 0, s, c, words4(y));
+  const dim3 block(QT_THREADS), grid = row_grid(ext_k);
+  switch (form) {
+    case B2F_FP_CANONICAL:
+      hipLaunchKernelGGL((quot_gates_kernel<Pallas, false>), grid, block, 0, s, a);
+      break;
+    case B2F_FP_MONTGOMERY:
+      hipLaunchKernelGGL((quot_gates_kernel<Pallas, true>), grid, block, 0, s, a);
+      break;
+    case B2F_FP_BN254_CANONICAL:
+      hipLaunchKernelGGL((quot_gates_kernel<Bn254, false>), grid, block, 0, s, a);
+      break;
+    default:
+      hipLaunchKernelGGL((quot_gates_kernel<Bn254, true>), grid, block, 0, s, a);
   }
   return hipGetLastError();
 }
