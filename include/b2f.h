@@ -507,6 +507,66 @@ B2F_API int b2f_quotient_divide_dev(b2f_ctx* ctx, uint32_t k, uint32_t ext_k, co
                                     const uint64_t shift[4], const uint64_t* d_h_in, uint64_t* d_h_out,
                                     uint32_t form, void* stream);
 
+/* The opening step over coefficient columns: multi-point evaluation, linear folds and Kate division
+ * (halo2_proofs 0.3.0 arithmetic.rs eval_polynomial and kate_division; the evaluations and the
+ * x^n fold of the h pieces in plonk/prover.rs; the x_1, x_2 and x_4 folds and the divisions of
+ * poly/multiopen/prover.rs). Field arithmetic only: the transcript, the commitments and the final
+ * IPA / KZG opening stay with the caller. The pieces of h are the columns of the inverse NTT's
+ * output (b2f_ntt_columns_dev, shift = ZETA) viewed with rows = n.
+ * Shared conventions: a column block is d[(c * rows + i) * 4 + limb] in `form` (any B2F_FP_*;
+ * inputs reduced, outputs fully reduced and in the same form: every pass is linear in the column
+ * data with Montgomery-form multipliers, which gives a canonical column exactly what converting at
+ * load and store would); len <= rows coefficients per column are read, at i < len, and rows >= len
+ * are never read or written; points and scalars are canonical host elements < p; every host array
+ * is consumed before the call returns; scratch belongs to the context; pointers are 16-byte
+ * aligned; no output may overlap an input. Errors, nothing launched and the next good call works:
+ * B2F_ERR_ARG for a null or misaligned pointer, form > 3, len == 0 (or > 2^32), n_cols == 0,
+ * n_queries == 0 / n_out == 0, a column or point index out of range, an h_first that does not
+ * start at 0 or decreases, an element >= p, a forbidden overlap; B2F_ERR_ROWS for len > rows or
+ * out_rows < len. Asynchronous on `stream`; each call is one B2F_KERNEL_QUOTIENT region.
+ *
+ * b2f_poly_eval_dev: d_out[q] = sum_{i < len} col[c_q][i] pt[p_q]^i for the query q =
+ * (h_queries[2 q], h_queries[2 q + 1]) = (column, point index), as n_queries elements in `form`.
+ * Queries come in any order and may repeat. The queries are grouped by column on the host and a
+ * column is read once per call, however many queries name it: a workgroup keeps a tile of 1,024
+ * coefficients in registers while it loops over the column's points; the tile sums are combined
+ * by a second launch. The power tables of the points are built on the device. */
+B2F_API int b2f_poly_eval_dev(b2f_ctx* ctx, const uint64_t* d_cols, uint64_t rows, uint64_t len, uint32_t n_cols,
+                              const uint64_t* h_points, uint32_t n_points, const uint32_t* h_queries,
+                              uint64_t n_queries, uint32_t form, uint64_t* d_out, void* stream);
+
+/* Output column o = sum_{j in [h_first[o], h_first[o + 1])} h_scalar[j] * column h_col[j], over
+ * i < len, at d_out[(o * out_rows + i) * 4 + limb]; an empty range gives zeros. h_first has
+ * n_out + 1 entries, h_col and h_scalar nnz = h_first[n_out]. Every challenge fold of the step is
+ * one of these: q = q x_1 + poly over a point set (scalars x_1^(m-1) .. 1), the x_2 and x_4 folds,
+ * and h(X) = sum_i x^(n i) h_i(X) (the host supplies the powers). One pass: an output row reads
+ * each of its inputs once. */
+B2F_API int b2f_poly_combine_dev(b2f_ctx* ctx, const uint64_t* d_cols, uint64_t rows, uint64_t len,
+                                 uint32_t n_cols, const uint32_t* h_first, const uint32_t* h_col,
+                                 const uint64_t* h_scalar, uint32_t n_out, uint32_t form, uint64_t* d_out,
+                                 uint64_t out_rows, void* stream);
+
+/* Output column c is halo2's kate_division applied to column c for the points h_points[h_first[c]]
+ * .. h_points[h_first[c + 1] - 1] in turn (h_first: n_cols + 1 entries): with m_c points, the
+ * floor quotient by prod (X - pt_j), remainders discarded. Its len - m_c coefficients are written
+ * and rows len - m_c <= i < len are written zero (halo2 resizes to n); m_c = 0 copies the column,
+ * m_c >= len gives all zeros. One division is q_{len-1} = 0, q_{i-1} = a_i + z q_i, a suffix
+ * recurrence with a constant multiplier: per point, one launch forms the tile sums (the evaluation
+ * kernel's), one scans them into carries, one applies them; a chain of several points repeats the
+ * three, ping-ponging through context scratch. */
+B2F_API int b2f_kate_divide_dev(b2f_ctx* ctx, const uint64_t* d_cols, uint64_t rows, uint64_t len,
+                                uint32_t n_cols, const uint32_t* h_first, const uint64_t* h_points,
+                                uint32_t form, uint64_t* d_out, uint64_t out_rows, void* stream);
+
+/* The advice queries of the chip: the (halo2 advice column, rotation) pairs the sixteen gates read
+ * (the list at b2f_quotient_gates_dev), as a set, sorted by column then rotation; writes
+ * min(count, cap) pairs (column, rotation) and returns count. These are the evaluations of advice
+ * columns a prover owes for the custom gates (the permutation and lookup arguments add their
+ * own); the fixed columns are all read at rotation 0. halo2 records queries in the order the
+ * gates first make them; that order is not modelled, as the combination of selectors is not.
+ * Host function. */
+B2F_API uint64_t b2f_gate_queries(uint32_t* pairs, uint64_t cap);
+
 /* Per-kernel timing with HIP events recorded on the launch stream around every kernel the
  * fill/eval calls launch (no host synchronization while recording). b2f_set_timing(ctx, 1)
  * clears the log and starts recording; b2f_kernel_times waits for the recorded events and
@@ -521,7 +581,8 @@ B2F_API int b2f_quotient_divide_dev(b2f_ctx* ctx, uint32_t k, uint32_t ext_k, co
 #define B2F_KERNEL_PERM 6   /* permutation-argument prover columns (all passes of one call) */
 #define B2F_KERNEL_PERM_SIGMA 7 /* permutation keygen: the sigma columns (b2f_permutation_sigma_dev) */
 #define B2F_KERNEL_NTT 8    /* NTT of prover columns (table build and all passes of one call) */
-#define B2F_KERNEL_QUOTIENT 9 /* quotient terms, the vanishing divide, the Lagrange selectors */
+#define B2F_KERNEL_QUOTIENT 9 /* quotient terms, the vanishing divide, the Lagrange selectors and the
+                                 evaluation / opening calls */
 #define B2F_NUM_KERNELS 10
 /* total_ms and count must each hold b2f_num_kernels() entries (= B2F_NUM_KERNELS of the
  * header the library was built with; it grew from 7 to 8 with B2F_KERNEL_PERM_SIGMA, to 9

@@ -7,5 +7,6 @@ from ._lib import (FP_BN254_CANONICAL, FP_BN254_MONTGOMERY, FP_CANONICAL, FP_MON
                    NTT_FORWARD, NTT_INVERSE, B2FError, EvalReport, load)
 from .layout import (INPUT_DTYPE, SELECTORS, as_inputs, halo2_column_index, offsets,  # noqa: F401
                      parse_eip152, rows, split_fixed)
-from .engine import DeviceBatch, Engine, copy_constraints, permutation_mapping  # noqa: F401
+from .engine import (DeviceBatch, Engine, copy_constraints, gate_queries,  # noqa: F401
+                     permutation_mapping)
 from . import field  # noqa: F401

@@ -127,6 +127,12 @@ SIGNATURES = [
                                       ctypes.c_uint32, P]),
     ("b2f_quotient_divide_dev", I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, P, P, P,
                                       ctypes.c_uint32, P]),
+    ("b2f_poly_eval_dev", I32, [P, P, U64, U64, ctypes.c_uint32, P, ctypes.c_uint32, P, U64,
+                                ctypes.c_uint32, P, P]),
+    ("b2f_poly_combine_dev", I32, [P, P, U64, U64, ctypes.c_uint32, P, P, P, ctypes.c_uint32,
+                                   ctypes.c_uint32, P, U64, P]),
+    ("b2f_kate_divide_dev", I32, [P, P, U64, U64, ctypes.c_uint32, P, P, ctypes.c_uint32, P, U64, P]),
+    ("b2f_gate_queries", U64, [P, U64]),
     ("b2f_sync", I32, [P, P]),
     ("b2f_fill", I32, [P, P, SIZE, P, P, P]),
     ("b2f_eval", I32, [P, P, P, P, SIZE, U64, P]),

@@ -3,6 +3,7 @@
 PyTorch is plumbing here (device memory, the stream handle); the work is the HIP kernels
 behind include/b2f.h.
 """
+import builtins  # the tensor-level opening calls take a `len` argument, as the ABI names it
 import ctypes
 import os
 
@@ -417,6 +418,106 @@ class Engine:
                                  h.data_ptr(), out.data_ptr(), form, s)
         return out
 
+    # ---------------------------------------------------------------- evaluations and openings
+    @staticmethod
+    def _elems(vals):
+        """Python ints as a uint64 [len, 4] host array of canonical little-endian limbs."""
+        try:
+            raw = b"".join(int(v).to_bytes(32, "little") for v in vals)
+        except OverflowError:
+            raise _lib.B2FError(_lib.ERR_ARG, "a field element is negative or above 2^256")
+        return np.frombuffer(raw, dtype=np.uint64).reshape(-1, 4).copy()
+
+    def poly_eval_dev(self, d_cols, rows, len_, n_cols, points, queries, form, d_out, stream=0):
+        """b2f_poly_eval_dev; points: Python ints (canonical), queries: (column, point index)
+        pairs."""
+        pts = self._elems(points)
+        qs = np.ascontiguousarray(queries, dtype=np.uint32).reshape(-1, 2)
+        self._check(self.lib.b2f_poly_eval_dev(
+            self.ctx, _vp(d_cols), int(rows), int(len_), int(n_cols), _np_ptr(pts), len(pts), _np_ptr(qs),
+            len(qs), int(form), _vp(d_out), _vp(stream)))
+
+    def poly_combine_dev(self, d_cols, rows, len_, n_cols, combos, form, d_out, out_rows, stream=0):
+        """b2f_poly_combine_dev; combos: one list of (column, scalar int) terms per output."""
+        first = np.zeros(len(combos) + 1, dtype=np.uint32)
+        for o, terms in enumerate(combos):
+            first[o + 1] = first[o] + len(terms)
+        col = np.array([t[0] for terms in combos for t in terms] + [0], dtype=np.uint32)
+        scal = self._elems([t[1] for terms in combos for t in terms] + [0])
+        self._check(self.lib.b2f_poly_combine_dev(
+            self.ctx, _vp(d_cols), int(rows), int(len_), int(n_cols), _np_ptr(first), _np_ptr(col),
+            _np_ptr(scal), len(combos), int(form), _vp(d_out), int(out_rows), _vp(stream)))
+
+    def kate_divide_dev(self, d_cols, rows, len_, n_cols, point_lists, form, d_out, out_rows, stream=0):
+        """b2f_kate_divide_dev; point_lists: one list of Python ints (canonical) per column."""
+        first = np.zeros(len(point_lists) + 1, dtype=np.uint32)
+        for c, pts in enumerate(point_lists):
+            first[c + 1] = first[c] + len(pts)
+        pts = self._elems([z for lst in point_lists for z in lst] + [0])
+        self._check(self.lib.b2f_kate_divide_dev(
+            self.ctx, _vp(d_cols), int(rows), int(len_), int(n_cols), _np_ptr(first), _np_ptr(pts),
+            int(form), _vp(d_out), int(out_rows), _vp(stream)))
+
+    @staticmethod
+    def _coeff_cols(name, t):
+        import torch
+
+        if t.dim() != 3 or t.shape[2] != 4 or t.dtype != torch.int64 or not t.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "%s must be contiguous int64 [n_cols, rows, 4]" % name)
+        return int(t.shape[0]), int(t.shape[1])
+
+    def poly_eval(self, cols, points, queries, len=None, form=_lib.FP_MONTGOMERY, stream=None):
+        """Evaluations of coefficient columns (b2f_poly_eval_dev). cols: int64 [n_cols, rows, 4] in
+        `form`, the first `len` rows (default: all) of each a polynomial's coefficients; points:
+        Python ints; queries: (column, point index) pairs in any order. Returns int64
+        [n_queries, 4] in `form`."""
+        import torch
+
+        n_cols, rows = self._coeff_cols("poly_eval: cols", cols)
+        n = rows if len is None else int(len)
+        qs = np.ascontiguousarray(queries, dtype=np.uint32).reshape(-1, 2)
+        out = torch.empty((qs.shape[0], 4), dtype=torch.int64, device=cols.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.poly_eval_dev(cols.data_ptr(), rows, n, n_cols, points, qs, form, out.data_ptr(), s)
+        return out
+
+    def poly_combine(self, cols, combos, len=None, form=_lib.FP_MONTGOMERY, out=None, stream=None):
+        """Linear combinations of coefficient columns (b2f_poly_combine_dev): output o is the sum
+        of scalar * cols[column] over the (column, scalar) terms of combos[o] (none: zeros), on the
+        first `len` rows. Returns int64 [n_out, len, 4] (`out`, when given: [n_out, rows >= len, 4],
+        rows past len untouched)."""
+        import torch
+
+        n_cols, rows = self._coeff_cols("poly_combine: cols", cols)
+        n = rows if len is None else int(len)
+        if out is None:
+            out = torch.empty((builtins.len(combos), n, 4), dtype=torch.int64, device=cols.device)
+        n_out, out_rows = self._coeff_cols("poly_combine: out", out)
+        if n_out != builtins.len(combos):
+            raise _lib.B2FError(_lib.ERR_ARG, "poly_combine: out must hold one column per output")
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.poly_combine_dev(cols.data_ptr(), rows, n, n_cols, combos, form, out.data_ptr(), out_rows, s)
+        return out
+
+    def kate_divide(self, cols, point_lists, len=None, form=_lib.FP_MONTGOMERY, out=None, stream=None):
+        """halo2's kate_division of column c by (X - z) for each z of point_lists[c] in turn
+        (b2f_kate_divide_dev), on the first `len` rows. Returns int64 [n_cols, len, 4] (`out`, when
+        given: [n_cols, rows >= len, 4], rows past len untouched)."""
+        import torch
+
+        n_cols, rows = self._coeff_cols("kate_divide: cols", cols)
+        n = rows if len is None else int(len)
+        if builtins.len(point_lists) != n_cols:
+            raise _lib.B2FError(_lib.ERR_ARG, "kate_divide: one point list per column")
+        if out is None:
+            out = torch.empty((n_cols, n, 4), dtype=torch.int64, device=cols.device)
+        n_out, out_rows = self._coeff_cols("kate_divide: out", out)
+        if n_out != n_cols:
+            raise _lib.B2FError(_lib.ERR_ARG, "kate_divide: out must hold one column per input")
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.kate_divide_dev(cols.data_ptr(), rows, n, n_cols, point_lists, form, out.data_ptr(), out_rows, s)
+        return out
+
     def debug_eval_path(self):
         """Path of the last eval_dev call (device-synchronizing): 0 the fast clean-check pass
         found the trace clean, 1 it flagged something and the exact eval kernel reported, 2 no
@@ -476,6 +577,16 @@ def copy_constraints(rounds):
     n = int(lib.b2f_copy_constraints(int(rounds), None, 0))
     out = np.zeros((n, 4), dtype=np.uint32)
     lib.b2f_copy_constraints(int(rounds), _np_ptr(out), n)
+    return out
+
+
+def gate_queries():
+    """The advice queries of the chip's sixteen gates: u32 [count, 2] (halo2 advice column,
+    rotation), sorted by column then rotation (b2f_gate_queries)."""
+    lib = _lib.load()
+    n = int(lib.b2f_gate_queries(None, 0))
+    out = np.zeros((n, 2), dtype=np.uint32)
+    lib.b2f_gate_queries(_np_ptr(out), n)
     return out
 
 

@@ -42,3 +42,12 @@ def omega(field, k):
 def limbs(v):
     """A field element as the 4 little-endian u64 limbs the ABI takes."""
     return [(int(v) >> (64 * i)) & (2**64 - 1) for i in range(4)]
+
+
+def rotated_points(f, x, k, rotations):
+    """x omega^r for each r of `rotations` (ints; a negative r goes by omega^-1) in the 2^k-row
+    domain of field f: the points halo2 evaluates a column queried at those rotations at."""
+    p = MODULUS[f]
+    w = omega(f, k)
+    wi = pow(w, p - 2, p)
+    return [int(x) * pow(w if r >= 0 else wi, abs(int(r)), p) % p for r in rotations]

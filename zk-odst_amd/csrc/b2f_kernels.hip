@@ -29,6 +29,7 @@
 
 #include "../../include/b2f.h"
 #include "b2f_common.h"
+#include "b2f_open.h"
 
 using namespace b2f;
 
@@ -92,6 +93,7 @@ hipError_t launch_quot_lookup(uint32_t k, uint32_t ext_k, const uint64_t* d_l, c
 hipError_t launch_quot_gates(uint32_t k, uint32_t ext_k, const uint64_t* d_advice, const uint64_t* d_fixed,
                              uint64_t rows, const uint64_t* y, const uint64_t* d_h_in, uint64_t* d_h_out,
                              uint32_t form, void* d_consts, hipStream_t s);
+uint64_t gate_queries(uint32_t* pairs, uint64_t cap);
 size_t quot_divisor_bytes(uint32_t k, uint32_t ext_k);
 hipError_t launch_quot_divisors(void* d_dtab, uint32_t form, uint32_t k, uint32_t ext_k, const uint64_t* omega,
                                 const uint64_t* shift, hipStream_t s);
@@ -1033,6 +1035,16 @@ struct b2f_ctx {
   QuotTab quot_tab[QUOT_TABS], quot_div[QUOT_TABS];
   uint32_t quot_next, quot_div_next;
   void* d_quot_consts;
+  // evaluation / opening calls (b2f_open.hip): the call's host arrays staged in pinned memory and
+  // uploaded asynchronously (as the permutation's instance table is), and the scratch
+  uint64_t* h_op;
+  size_t h_op_cap;  // in u64 words
+  hipEvent_t op_ev;
+  bool op_ev_live;
+  void* d_op_blob;
+  size_t op_blob_cap;  // in u64 words
+  void* d_op;
+  size_t op_cap;
 };
 
 namespace {
@@ -1313,6 +1325,11 @@ B2F_API void b2f_destroy(b2f_ctx* ctx) {
   for (auto& t : ctx->quot_tab) (void)hipFree(t.d);
   for (auto& t : ctx->quot_div) (void)hipFree(t.d);
   (void)hipFree(ctx->d_quot_consts);
+  (void)hipFree(ctx->d_op_blob);
+  (void)hipFree(ctx->d_op);
+  if (ctx->op_ev_live) (void)hipEventSynchronize(ctx->op_ev);
+  if (ctx->op_ev) (void)hipEventDestroy(ctx->op_ev);
+  (void)hipHostFree(ctx->h_op);
   if (ctx->pm_inst_ev_live) (void)hipEventSynchronize(ctx->pm_inst_ev);
   if (ctx->pm_inst_ev) (void)hipEventDestroy(ctx->pm_inst_ev);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
@@ -2104,6 +2121,61 @@ int quot_consts(b2f_ctx* ctx) {
   return B2F_OK;
 }
 
+// The host part the evaluation / opening calls share: stage the plan's image in pinned memory,
+// grow the device blocks if needed and upload the image on the stream. The host waits only for the
+// previous call's upload (so the staging can be rewritten), or for the whole stream when a device
+// block has to grow.
+int open_upload(b2f_ctx* ctx, const OpenPlan& p, hipStream_t s) {
+  const size_t words = p.blob.size() + 2, scratch = p.scratch_bytes + 256;
+  if (ctx->op_ev_live) {
+    HIPCHK(ctx, hipEventSynchronize(ctx->op_ev));
+    ctx->op_ev_live = false;
+  }
+  if (!ctx->op_ev) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->op_ev, hipEventDisableTiming));
+  if (words > ctx->h_op_cap) {
+    if (ctx->h_op) HIPCHK(ctx, hipHostFree(ctx->h_op));
+    ctx->h_op = nullptr;
+    ctx->h_op_cap = 0;
+    HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_op, 8 * words, hipHostMallocDefault));
+    ctx->h_op_cap = words;
+  }
+  if (words > ctx->op_blob_cap || scratch > ctx->op_cap) {  // earlier calls may still read the blocks
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (words > ctx->op_blob_cap) {
+      if (ctx->d_op_blob) HIPCHK(ctx, hipFree(ctx->d_op_blob));
+      ctx->d_op_blob = nullptr;
+      ctx->op_blob_cap = 0;
+      HIPCHK(ctx, hipMalloc(&ctx->d_op_blob, 8 * words));
+      ctx->op_blob_cap = words;
+    }
+    if (scratch > ctx->op_cap) {
+      if (ctx->d_op) HIPCHK(ctx, hipFree(ctx->d_op));
+      ctx->d_op = nullptr;
+      ctx->op_cap = 0;
+      HIPCHK(ctx, hipMalloc(&ctx->d_op, scratch));
+      ctx->op_cap = scratch;
+    }
+  }
+  memcpy(ctx->h_op, p.blob.data(), 8 * p.blob.size());
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d_op_blob, ctx->h_op, 8 * p.blob.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipEventRecord(ctx->op_ev, s));
+  ctx->op_ev_live = true;
+  return B2F_OK;
+}
+
+// The argument checks the three calls share: the column block and its sizes.
+int open_check_cols(b2f_ctx* ctx, const char* what, const uint64_t* d_cols, uint64_t rows, uint64_t len,
+                    uint32_t n_cols, uint32_t form, const uint64_t* d_out) {
+  if (!d_cols || !d_out) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (((uintptr_t)d_cols | (uintptr_t)d_out) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "%s: buffers must be 16-byte aligned", what);
+  if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "%s: unknown form %u", what, form);
+  if (len == 0 || n_cols == 0) return set_err(ctx, B2F_ERR_ARG, "%s: no columns or no coefficients", what);
+  if (len > rows) return set_err(ctx, B2F_ERR_ROWS, "%s: len %llu > rows", what, (unsigned long long)len);
+  if (rows > (1ull << 58) / n_cols) return set_err(ctx, B2F_ERR_ARG, "%s: column stride overflows the address space", what);
+  return B2F_OK;
+}
+
 #ifdef B2F_DIAG
 // Diagnostics build only: B2F_DIAG_NTT_PLAN=l1,l2[,l3[,l4]] read at the call replaces the pass plan
 // of b2f_ntt_columns_dev (tests/test_gpu_ntt_plans.py: plans the product never picks at small k).
@@ -2291,6 +2363,83 @@ B2F_API int b2f_quotient_divide_dev(b2f_ctx* ctx, uint32_t k, uint32_t ext_k, co
   timed_end(ctx, tk, s);
   return B2F_OK;
 }
+
+B2F_API int b2f_poly_eval_dev(b2f_ctx* ctx, const uint64_t* d_cols, uint64_t rows, uint64_t len, uint32_t n_cols,
+                              const uint64_t* h_points, uint32_t n_points, const uint32_t* h_queries,
+                              uint64_t n_queries, uint32_t form, uint64_t* d_out, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "poly eval";
+  if (!h_points || !h_queries) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (int rc = open_check_cols(ctx, what, d_cols, rows, len, n_cols, form, d_out)) return rc;
+  if (n_points == 0 || n_queries == 0) return set_err(ctx, B2F_ERR_ARG, "%s: no points or no queries", what);
+  OpenPlan plan;
+  char msg[160];
+  if (int rc = open_plan_eval(plan, len, n_cols, h_points, n_points, h_queries, n_queries, form, msg, sizeof msg))
+    return set_err(ctx, rc, "%s: %s", what, msg);
+  if (ranges_overlap(d_out, 32 * n_queries, d_cols, (uint64_t)n_cols * rows * 32))
+    return set_err(ctx, B2F_ERR_ARG, "%s: the output overlaps the columns", what);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = open_upload(ctx, plan, s)) return rc;
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_poly_eval(plan, d_cols, rows, ctx->d_op_blob, ctx->d_op, d_out, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API int b2f_poly_combine_dev(b2f_ctx* ctx, const uint64_t* d_cols, uint64_t rows, uint64_t len,
+                                 uint32_t n_cols, const uint32_t* h_first, const uint32_t* h_col,
+                                 const uint64_t* h_scalar, uint32_t n_out, uint32_t form, uint64_t* d_out,
+                                 uint64_t out_rows, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "poly combine";
+  if (!h_first) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (int rc = open_check_cols(ctx, what, d_cols, rows, len, n_cols, form, d_out)) return rc;
+  if (n_out == 0) return set_err(ctx, B2F_ERR_ARG, "%s: no outputs", what);
+  if (out_rows < len) return set_err(ctx, B2F_ERR_ROWS, "%s: out_rows < len", what);
+  if (out_rows > (1ull << 58) / n_out) return set_err(ctx, B2F_ERR_ARG, "%s: column stride overflows the address space", what);
+  if (h_first[n_out] && (!h_col || !h_scalar)) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  OpenPlan plan;
+  char msg[160];
+  if (int rc = open_plan_combine(plan, len, n_cols, h_first, h_col, h_scalar, n_out, form, msg, sizeof msg))
+    return set_err(ctx, rc, "%s: %s", what, msg);
+  if (ranges_overlap(d_out, (uint64_t)n_out * out_rows * 32, d_cols, (uint64_t)n_cols * rows * 32))
+    return set_err(ctx, B2F_ERR_ARG, "%s: the output overlaps the columns", what);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = open_upload(ctx, plan, s)) return rc;
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_poly_combine(plan, d_cols, rows, ctx->d_op_blob, ctx->d_op, d_out, out_rows, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API int b2f_kate_divide_dev(b2f_ctx* ctx, const uint64_t* d_cols, uint64_t rows, uint64_t len,
+                                uint32_t n_cols, const uint32_t* h_first, const uint64_t* h_points,
+                                uint32_t form, uint64_t* d_out, uint64_t out_rows, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "kate divide";
+  if (!h_first) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (int rc = open_check_cols(ctx, what, d_cols, rows, len, n_cols, form, d_out)) return rc;
+  if (out_rows < len) return set_err(ctx, B2F_ERR_ROWS, "%s: out_rows < len", what);
+  if (out_rows > (1ull << 58) / n_cols) return set_err(ctx, B2F_ERR_ARG, "%s: column stride overflows the address space", what);
+  if (h_first[n_cols] && !h_points) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  OpenPlan plan;
+  char msg[160];
+  if (int rc = open_plan_kate(plan, len, n_cols, h_first, h_points, form, msg, sizeof msg))
+    return set_err(ctx, rc, "%s: %s", what, msg);
+  if (ranges_overlap(d_out, (uint64_t)n_cols * out_rows * 32, d_cols, (uint64_t)n_cols * rows * 32))
+    return set_err(ctx, B2F_ERR_ARG, "%s: the output overlaps the columns", what);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = open_upload(ctx, plan, s)) return rc;
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_kate_divide(plan, d_cols, rows, ctx->d_op_blob, ctx->d_op, d_out, out_rows, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API uint64_t b2f_gate_queries(uint32_t* pairs, uint64_t cap) { return gate_queries(pairs, cap); }
 
 B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_rows,
                                 uint64_t in_len, uint32_t n_cols, uint32_t k,

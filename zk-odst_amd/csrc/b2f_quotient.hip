@@ -251,6 +251,33 @@ constexpr uint32_t GA0 = 7, GA1 = 8, GA2 = 9, GA3 = 1, GA4 = 2, GA5 = 0, GA6 = 3
 constexpr uint32_t QG_TERMS = 74;
 constexpr uint32_t QG_COUNT[16] = {2, 8, 8, 2, 12, 2, 4, 2, 12, 2, 4, 2, 4, 4, 1, 5};
 
+// The cells quot_gates_kernel reads: QG_READS[g][i] has bit j set when gate g reads a_i@j (the
+// A(GAi, j) calls of the kernel's blocks, gate by gate; k_0 and the selectors are fixed columns,
+// all at rotation 0). b2f_gate_queries is the union over the gates. The kernel is unrolled by
+// hand, so nothing derives one from the other at compile time: tests/test_open_ref.py pins this
+// table to the gate polynomials of tests/quotient_gates_ref.py, gate by gate through the union,
+// and tests/test_gpu_open.py evaluates the chip's own quotient at a point through it.
+constexpr uint16_t R0123 = 0x00f, R0246 = 0x055, R0369 = 0x249, R147A = 0x492, R07 = 0x0ff, R0B = 0xfff;
+constexpr uint16_t QG_READS[16][10] = {
+    //  a_0     a_1            a_2            a_3    a_4    a_5    a_6    a_7    a_8    a_9
+    {0, R0123, 0, 0, 0, 0, 0, 1, 1, 0},                                 // 0
+    {0, R0369 | R147A, R0369 | R147A, 0, 0, 0, 0, R0369, R0369, 0},      // 1
+    {0, R0246, R0246, 0, 0, 0, R0246, R0246, R0246, 0},                  // 2
+    {0, R0123, 0, R0123, R0123, R0123, 0, 0, 0, 1},                      // 3
+    {R0369 | (R0369 << 1), 0, R0B, R0369, R0369, 0, 0, 0, 0, 0},         // 4
+    {0, R0123, 0, R0123, R0123, 0, 0, 0, 0, 1},                          // 5
+    {0, 0, R07, R0246, R0246, 0, 0, 0, 0, 0},                            // 6
+    {0, R0123, 0, R0123, R0123, R0123, 0, 0, 0, 1},                      // 7
+    {R0246, 0, R07, R0246, R0246, 0, R0246, 0, 0, 0},                    // 8
+    {0, R0123, 0, R0123, R0123, 0, 0, 0, 0, 1},                          // 9
+    {0, 0, R07, R0246, R0246, 0, 0, 0, 0, 0},                            // 10
+    {0, R0246, 0, 0, 0, 0, 0, 1, 1, 0},                                  // 11
+    {0, 0, R07, R0246, R0246, 0, 0, 0, 0, 0},                            // 12
+    {0, 0, R07, R0246, R0246, R0246, 0, 0, 0, 0},                        // 13
+    {0, 1, 0, 0, 0, 0, 0, 0, 0, 0},                                      // 14
+    {0, R0123, 0, 0, 0, 1, 0, 0, 0, 0},                                  // 15
+};
+
 struct GateConsts {
   Fe y, yt;      // y, y^74
   Fe ys[16];     // y^S_g, S_g = the number of terms after gate g's last one
@@ -485,6 +512,26 @@ void launch_consts(uint32_t form, void* d_consts, const uint64_t* beta, const ui
 size_t quot_xtab_bytes(uint32_t ext_k) {
   const uint32_t h0 = quot_h0(ext_k);
   return 32ull * (QT_T0_OFF + (1ull << h0) + (1ull << (ext_k - h0)));
+}
+
+// b2f_gate_queries: the union of QG_READS over the gates as (halo2 column, rotation) pairs, sorted
+// by column then rotation
+uint64_t gate_queries(uint32_t* pairs, uint64_t cap) {
+  static const uint32_t halo2[10] = {GA0, GA1, GA2, GA3, GA4, GA5, GA6, GA7, GA8, GA9};
+  uint16_t by_col[10] = {};
+  for (int g = 0; g < 16; g++)
+    for (int i = 0; i < 10; i++) by_col[halo2[i]] |= QG_READS[g][i];
+  uint64_t count = 0;
+  for (uint32_t c = 0; c < 10; c++)
+    for (uint32_t j = 0; j < 16; j++)
+      if ((by_col[c] >> j) & 1u) {
+        if (pairs && count < cap) {
+          pairs[2 * count] = c;
+          pairs[2 * count + 1] = j;
+        }
+        count++;
+      }
+  return count;
 }
 
 // one block serves both kinds of term call
