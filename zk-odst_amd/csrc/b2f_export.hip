@@ -27,6 +27,7 @@
 
 #include "../../include/b2f.h"
 #include "b2f_field.h"
+#include "b2f_launch.h"
 
 namespace b2f {
 

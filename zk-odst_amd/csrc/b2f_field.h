@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "b2f_safegcd.h"
 
 namespace b2f {
@@ -53,6 +55,34 @@ struct Bn254 {
 };
 
 static_assert(Pallas::P[7] < 0x7ffffffeu && Bn254::P[7] < 0x7ffffffeu, "no-carry CIOS needs a spare top bit");
+
+// Host-side dispatch on a B2F_FP_* form (bit 1: the field, bit 0: Montgomery form), for launching
+// kernel<F> or kernel<F, MONT>: with_field calls fn(Pallas{}) or fn(Bn254{}) and returns what it
+// returns, with_form calls fn(F{}, std::bool_constant<MONT>{}).
+template <class Fn>
+auto with_field(uint32_t form, Fn&& fn) {
+  if ((form >> 1) & 1u) return fn(Bn254{});
+  return fn(Pallas{});
+}
+template <class Fn>
+void with_form(uint32_t form, Fn&& fn) {
+  with_field(form, [&](auto f) {
+    if (form & 1u) fn(f, std::true_type{});
+    else fn(f, std::false_type{});
+  });
+}
+
+// v (four little-endian u64 limbs, host memory) < the modulus of the field `form` selects
+inline bool fe_canonical(uint32_t form, const uint64_t* v) {
+  return with_field(form, [v](auto f) {
+    using F = decltype(f);
+    for (int i = 3; i >= 0; i--) {
+      const uint64_t p = ((uint64_t)F::P[2 * i + 1] << 32) | F::P[2 * i];
+      if (v[i] != p) return v[i] < p;
+    }
+    return false;
+  });
+}
 
 struct Fe {
   uint32_t w[8];
@@ -592,4 +622,17 @@ __device__ __forceinline__ Fe load_words(const uint64_t* c) {  // 4 LE u64 limbs
 }
 
 }  // namespace field
+
+// A field element as a kernel argument (four little-endian u64 limbs; load_words reads it). The
+// kernels taking one live in their file's unnamed namespace, and so does the type.
+namespace {
+struct Words4 {
+  uint64_t v[4];
+};
+inline Words4 words4(const uint64_t* v) {
+  Words4 w;
+  for (int i = 0; i < 4; i++) w.v[i] = v[i];
+  return w;
+}
+}  // namespace
 }  // namespace b2f

@@ -32,6 +32,7 @@
 
 #include "../../include/b2f.h"
 #include "b2f_common.h"
+#include "b2f_launch.h"
 
 typedef int32_t b2f_i32x4 __attribute__((ext_vector_type(4)));
 // the raw buffer store intrinsic (declared as CK's amd_buffer_addressing.hpp does)

@@ -1,0 +1,108 @@
+// b2f_launch.h -- the launch API between the C entry points (b2f_kernels.hip, b2f_api_prover.hip)
+// and the files that define the kernels. Each defining file includes it too, so a signature that
+// drifts from its declaration fails to link (the libraries are linked with --no-undefined). The
+// evaluation / opening calls' launchers take a host plan and are declared with it in b2f_open.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/b2f.h"
+
+namespace b2f {
+
+// b2f_lookup.hip
+size_t lookup_scratch_bytes(uint32_t group, uint64_t usable_rows);
+hipError_t launch_lookup(const uint32_t* d_advice, uint64_t total_rows,
+                         const uint64_t* d_row_begin, uint32_t n_circuits, uint64_t usable_rows,
+                         const uint64_t* theta, const uint64_t* beta, const uint64_t* gamma,
+                         uint32_t form, uint64_t* d_out, uint64_t out_rows, uint64_t* d_first_bad,
+                         void* scratch, uint32_t group, int* sticky, hipStream_t s2,
+                         hipEvent_t ev_fork, hipEvent_t ev_join, hipStream_t s3, hipEvent_t ev_tab,
+                         hipEvent_t ev_sorted, hipStream_t s);
+hipError_t launch_spread_table(uint64_t usable_rows, uint32_t form, uint64_t* d_out,
+                               uint64_t out_rows, hipStream_t s);
+
+// b2f_perm.hip
+size_t perm_scratch_bytes(uint32_t k, uint64_t usable_rows, size_t n_inst, uint32_t chunk_len);
+size_t perm_sigma_scratch_bytes(uint32_t k);
+size_t perm_batch_scratch_bytes(uint32_t k, uint64_t usable_rows, uint32_t group, uint32_t chunk_len);
+uint32_t perm_batch_group(uint64_t usable_rows, uint32_t n_circuits, uint32_t chunk_len);
+uint32_t perm_circ_words();
+hipError_t launch_permutation_sigma(const uint64_t* d_inst, size_t n_inst, const uint32_t* d_pool, uint32_t k,
+                                    const uint64_t* omega, const uint64_t* delta, uint32_t form,
+                                    uint64_t* d_sigma, uint64_t out_rows, void* scratch, hipStream_t s);
+hipError_t launch_permutation(const uint32_t* d_advice, uint64_t total_rows, uint64_t row0,
+                              const uint64_t* d_inst, size_t n_inst, const uint32_t* d_pool,
+                              uint32_t k, uint64_t usable_rows, const uint64_t* omega,
+                              const uint64_t* delta, const uint64_t* beta, const uint64_t* gamma,
+                              uint32_t chunk_len, uint32_t form, uint64_t* d_sigma, uint64_t* d_z,
+                              uint64_t out_rows, void* scratch, int* sticky, hipStream_t s2,
+                              hipEvent_t ev_fork, hipEvent_t ev_join, hipStream_t s);
+hipError_t launch_permutation_batch(const uint32_t* d_advice, uint64_t total_rows, const uint64_t* d_tab,
+                                    uint32_t n_circuits, uint32_t group, const uint32_t* d_pool,
+                                    uint32_t k, uint64_t usable_rows, const uint64_t* omega,
+                                    const uint64_t* delta, const uint64_t* beta, const uint64_t* gamma,
+                                    uint32_t chunk_len, uint32_t form, uint64_t* d_z, uint64_t out_rows,
+                                    void* scratch, int* sticky, hipStream_t s2, hipEvent_t ev_fork,
+                                    hipEvent_t ev_join, hipStream_t s);
+
+// b2f_ntt.hip
+size_t ntt_table_bytes(uint32_t k);
+hipError_t launch_ntt_tables(void* d_tab, uint32_t form, uint32_t k, const uint64_t* omega,
+                             const uint64_t* shift, uint32_t direction, hipStream_t s);
+hipError_t launch_ntt(const uint64_t* d_in, uint64_t in_rows, uint64_t in_len, uint32_t n_cols,
+                      uint32_t k, uint32_t form, uint32_t direction, bool shift_is_one, uint64_t* d_out,
+                      uint64_t out_rows, const void* d_tab, int* sticky, hipStream_t s,
+                      const uint32_t* plan = nullptr);
+void ntt_plan_of(uint32_t k, uint32_t* out);
+
+// b2f_quotient.hip
+size_t quot_xtab_bytes(uint32_t ext_k);
+size_t quot_consts_bytes();
+hipError_t launch_quot_xtab(void* d_tab, uint32_t form, uint32_t ext_k, const uint64_t* omega,
+                            const uint64_t* shift, hipStream_t s);
+hipError_t launch_lagrange_selectors(uint32_t k, uint32_t usable_rows, uint32_t form, uint64_t* d_out,
+                                     uint64_t out_rows, hipStream_t s);
+hipError_t launch_quot_permutation(uint32_t k, uint32_t ext_k, uint32_t usable_rows, const uint64_t* d_l,
+                                   const uint64_t* d_advice, const uint64_t* d_sigma, const uint64_t* d_z,
+                                   uint32_t chunk_len, uint64_t rows, const uint64_t* delta,
+                                   const uint64_t* beta, const uint64_t* gamma, const uint64_t* y,
+                                   const uint64_t* d_h_in, uint64_t* d_h_out, uint32_t form, uint32_t colmap,
+                                   const void* d_xtab, void* d_consts, int* sticky, hipStream_t s);
+hipError_t launch_quot_lookup(uint32_t k, uint32_t ext_k, const uint64_t* d_l, const uint64_t* d_lookup,
+                              uint64_t rows, const uint64_t* beta, const uint64_t* gamma, const uint64_t* y,
+                              const uint64_t* d_h_in, uint64_t* d_h_out, uint32_t form, void* d_consts,
+                              hipStream_t s);
+hipError_t launch_quot_gates(uint32_t k, uint32_t ext_k, const uint64_t* d_advice, const uint64_t* d_fixed,
+                             uint64_t rows, const uint64_t* y, const uint64_t* d_h_in, uint64_t* d_h_out,
+                             uint32_t form, void* d_consts, hipStream_t s);
+uint64_t gate_queries(uint32_t* pairs, uint64_t cap);
+size_t quot_divisor_bytes(uint32_t k, uint32_t ext_k);
+hipError_t launch_quot_divisors(void* d_dtab, uint32_t form, uint32_t k, uint32_t ext_k, const uint64_t* omega,
+                                const uint64_t* shift, hipStream_t s);
+hipError_t launch_quot_divide(uint32_t k, uint32_t ext_k, const uint64_t* d_h_in, uint64_t* d_h_out,
+                              uint32_t form, const void* d_dtab, int* sticky, hipStream_t s);
+
+// b2f_export.hip
+hipError_t launch_export_fp(const uint32_t* d_advice, uint64_t total_rows, uint64_t row_begin,
+                            uint64_t nrows, uint32_t form, uint64_t* d_out, uint64_t out_rows,
+                            int cu_count, unsigned* tctr, hipStream_t s);
+hipError_t launch_export_fixed_fp(const uint32_t* d_fixed, uint64_t row_begin, uint64_t nrows,
+                                  uint32_t form, uint64_t* d_out, uint64_t out_rows, hipStream_t s);
+
+// b2f_fused.hip
+size_t fused_scratch_bytes(uint64_t tiles);
+uint64_t fused_instance_tiles(uint64_t total_rows, uint64_t n);
+hipError_t launch_eval_fast(const uint32_t* d_adv, const uint32_t* d_fixed, const uint64_t* d_off, uint32_t n,
+                            uint64_t total_rows, void* scratch, uint64_t tiles, const int* d_status,
+                            int cu_count, hipStream_t s, const uint32_t** gate, int mode);
+hipError_t launch_fill_eval(const b2f_input* d_in, uint32_t n, const uint64_t* d_off,
+                            uint64_t total_rows, const uint64_t* rec, uint32_t* d_adv,
+                            uint32_t* d_fixed, void* scratch, uint64_t tiles,
+                            b2f_eval_report* d_rep, const int* d_status, uint64_t inj_row,
+                            uint32_t inj_col, uint32_t inj_mask, int mode, int cu_count,
+                            unsigned long long* clk, const uint64_t* seg, uint64_t seg_cap,
+                            hipStream_t s);
+
+}  // namespace b2f

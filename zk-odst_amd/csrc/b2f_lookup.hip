@@ -43,6 +43,7 @@
 #include "../../include/b2f.h"
 #include "b2f_field.h"
 #include "b2f_gprod.h"
+#include "b2f_launch.h"
 
 namespace b2f {
 
@@ -1301,11 +1302,10 @@ hipError_t launch_lookup(const uint32_t* d_advice, uint64_t total_rows,
     ch.gamma[i] = gamma[i];
   }
   const bool mont = (form & 1u) != 0;
-  if (form >> 1)
-    return run_lookup<field::Bn254>(d_advice, total_rows, d_row_begin, n_circuits, usable_rows, ch,
-                                    mont, d_out, out_rows, d_first_bad, scratch, group, sticky, side, ss, s);
-  return run_lookup<field::Pallas>(d_advice, total_rows, d_row_begin, n_circuits, usable_rows, ch,
-                                   mont, d_out, out_rows, d_first_bad, scratch, group, sticky, side, ss, s);
+  return field::with_field(form, [&](auto f) {
+    return run_lookup<decltype(f)>(d_advice, total_rows, d_row_begin, n_circuits, usable_rows, ch, mont, d_out,
+                                   out_rows, d_first_bad, scratch, group, sticky, side, ss, s);
+  });
 }
 
 }  // namespace b2f

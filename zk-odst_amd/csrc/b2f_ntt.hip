@@ -31,6 +31,7 @@
 
 #include "../../include/b2f.h"
 #include "b2f_field.h"
+#include "b2f_launch.h"
 
 namespace b2f {
 
@@ -59,10 +60,6 @@ struct NttHeader {
   uint32_t pad[15];
 };
 static_assert(sizeof(NttHeader) == NT_W_OFF * 32, "header = 8 elements");
-
-struct Words4 {
-  uint64_t v[4];
-};
 
 struct NttPass {
   const uint64_t* src;
@@ -356,22 +353,14 @@ size_t ntt_table_bytes(uint32_t k) {
 // Fill a table block for (field of form, k, omega, shift, direction).
 hipError_t launch_ntt_tables(void* d_tab, uint32_t form, uint32_t k, const uint64_t* omega,
                              const uint64_t* shift, uint32_t direction, hipStream_t s) {
-  Words4 w, sh;
-  for (int i = 0; i < 4; i++) {
-    w.v[i] = omega[i];
-    sh.v[i] = shift[i];
-  }
   uint64_t* tab = static_cast<uint64_t*>(d_tab);
   const uint32_t h0 = ntt_h0(k), mlog = k < NT_LOG ? k : NT_LOG;
   const uint32_t total = (1u << (mlog - 1)) + 2u * ((1u << h0) + (1u << (k - h0)));
-  const bool bn = (form >> 1) & 1u;
-  if (bn) {
-    hipLaunchKernelGGL(ntt_setup_kernel<Bn254>, dim3(1), dim3(64), 0, s, tab, w, sh, k, direction);
-    hipLaunchKernelGGL(ntt_tables_kernel<Bn254>, dim3((total + 255) / 256), dim3(256), 0, s, tab, k);
-  } else {
-    hipLaunchKernelGGL(ntt_setup_kernel<Pallas>, dim3(1), dim3(64), 0, s, tab, w, sh, k, direction);
-    hipLaunchKernelGGL(ntt_tables_kernel<Pallas>, dim3((total + 255) / 256), dim3(256), 0, s, tab, k);
-  }
+  with_field(form, [&](auto f) {
+    using F = decltype(f);
+    hipLaunchKernelGGL(ntt_setup_kernel<F>, dim3(1), dim3(64), 0, s, tab, words4(omega), words4(shift), k, direction);
+    hipLaunchKernelGGL(ntt_tables_kernel<F>, dim3((total + 255) / 256), dim3(256), 0, s, tab, k);
+  });
   return hipGetLastError();
 }
 
@@ -401,7 +390,6 @@ hipError_t launch_ntt(const uint64_t* d_in, uint64_t in_rows, uint64_t in_len, u
   a.mlog = k < NT_LOG ? k : NT_LOG;
   a.prescale = direction == B2F_NTT_FORWARD && !shift_is_one;
   a.postscale = direction == B2F_NTT_INVERSE;
-  const bool bn = (form >> 1) & 1u;
   const uint32_t per_y = a.P == 1 ? NT >> k : 1u;  // columns per grid row
   const uint32_t tiles = a.P == 1 ? 1u : 1u << (k - NT_LOG);
   const uint64_t max_cols = 65535ull * per_y;
@@ -411,8 +399,8 @@ hipError_t launch_ntt(const uint64_t* d_in, uint64_t in_rows, uint64_t in_len, u
     a.col0 = (uint32_t)c0;
     for (uint32_t p = 0; p < a.P; p++) {
       a.p = p;
-      if (bn) hipLaunchKernelGGL(ntt_pass_kernel<Bn254>, grid, dim3(NT_THREADS), 0, s, a);
-      else hipLaunchKernelGGL(ntt_pass_kernel<Pallas>, grid, dim3(NT_THREADS), 0, s, a);
+      with_field(form,
+                 [&](auto f) { hipLaunchKernelGGL(ntt_pass_kernel<decltype(f)>, grid, dim3(NT_THREADS), 0, s, a); });
     }
   }
   return hipGetLastError();

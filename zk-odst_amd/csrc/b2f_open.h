@@ -1,5 +1,5 @@
 // b2f_open.h -- the host plan of an evaluation / opening call (b2f_open.hip), shared with the C
-// entry points in b2f_kernels.hip. A plan is the host image of the call's device tables (the
+// entry points in b2f_api_prover.hip. A plan is the host image of the call's device tables (the
 // points, scalars and index lists of the host arrays, grouped as the kernels read them) plus the
 // sizes of the device scratch the launches carve. The entry point stages the image in pinned
 // memory, uploads it on the call's stream and hands both device blocks to the launcher.

@@ -336,24 +336,6 @@ __global__ __launch_bounds__(OP_THREADS) void kate_special_kernel(const KateArgs
   store(a.out + 4ull * (d.col * a.out_rows + i), d.zero ? fe_zero() : load(a.cols + 4ull * (d.col * a.rows + i)));
 }
 
-#define OPEN_LAUNCH(form, kernel, grid, block, s, ...)                              \
-  do {                                                                              \
-    if (((form) >> 1) & 1u)                                                         \
-      hipLaunchKernelGGL(kernel<Bn254>, grid, block, 0, s, __VA_ARGS__);            \
-    else                                                                            \
-      hipLaunchKernelGGL(kernel<Pallas>, grid, block, 0, s, __VA_ARGS__);           \
-  } while (0)
-
-bool canonical(uint32_t form, const uint64_t* v) {
-  static const uint64_t moduli[2][4] = {
-      {0x992d30ed00000001ull, 0x224698fc094cf91bull, 0, 0x4000000000000000ull},
-      {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull}};
-  const uint64_t* p = moduli[(form >> 1) & 1u];
-  for (int i = 3; i >= 0; i--)
-    if (v[i] != p[i]) return v[i] < p[i];
-  return false;
-}
-
 // append a section to the image at a 16-byte boundary; returns its offset in words
 size_t blob_put(std::vector<uint64_t>& blob, const void* data, size_t bytes) {
   if (blob.size() & 1u) blob.push_back(0);
@@ -383,8 +365,10 @@ int plan_common(OpenPlan& p, uint64_t len, uint32_t form, char* msg, size_t n) {
 
 void launch_pow_table(const OpenPlan& p, const uint64_t* d_blob, uint64_t* tab, hipStream_t s) {
   const uint64_t total = (uint64_t)p.n_points * (OP_THREADS + 1);
-  OPEN_LAUNCH(p.form, pow_table_kernel, dim3((uint32_t)((total + OP_THREADS - 1) / OP_THREADS)), dim3(OP_THREADS), s,
-              tab, d_blob + p.off_points, p.n_points);
+  with_field(p.form, [&](auto f) {
+    hipLaunchKernelGGL(pow_table_kernel<decltype(f)>, dim3((uint32_t)((total + OP_THREADS - 1) / OP_THREADS)),
+                       dim3(OP_THREADS), 0, s, tab, d_blob + p.off_points, p.n_points);
+  });
 }
 
 }  // namespace
@@ -397,7 +381,7 @@ int open_plan_eval(OpenPlan& p, uint64_t len, uint32_t n_cols, const uint64_t* h
     return B2F_ERR_ARG;
   }
   for (uint32_t i = 0; i < n_points; i++)
-    if (!canonical(form, h_points + 4ull * i)) {
+    if (!fe_canonical(form, h_points + 4ull * i)) {
       snprintf(msg, msg_len, "point %u is >= p", i);
       return B2F_ERR_ARG;
     }
@@ -453,11 +437,14 @@ hipError_t launch_poly_eval(const OpenPlan& p, const uint64_t* d_cols, uint64_t 
   a.partial = tab + align256(32ull * OP_PW * p.n_points) / 8;
   a.out = d_out;
   launch_pow_table(p, blob, tab, s);
-  for (uint32_t g0 = 0; g0 < p.n_groups; g0 += OP_MAX_Y) {
-    const uint32_t gn = p.n_groups - g0 < OP_MAX_Y ? p.n_groups - g0 : OP_MAX_Y;
-    OPEN_LAUNCH(p.form, poly_eval_partial_kernel, dim3((uint32_t)p.ntiles, gn), dim3(OP_THREADS), s, a, g0);
-  }
-  OPEN_LAUNCH(p.form, poly_eval_combine_kernel, dim3((uint32_t)p.n_queries), dim3(OP_THREADS), s, a);
+  with_field(p.form, [&](auto f) {
+    using F = decltype(f);
+    for (uint32_t g0 = 0; g0 < p.n_groups; g0 += OP_MAX_Y) {
+      const uint32_t gn = p.n_groups - g0 < OP_MAX_Y ? p.n_groups - g0 : OP_MAX_Y;
+      hipLaunchKernelGGL(poly_eval_partial_kernel<F>, dim3((uint32_t)p.ntiles, gn), dim3(OP_THREADS), 0, s, a, g0);
+    }
+    hipLaunchKernelGGL(poly_eval_combine_kernel<F>, dim3((uint32_t)p.n_queries), dim3(OP_THREADS), 0, s, a);
+  });
   return hipGetLastError();
 }
 
@@ -479,7 +466,7 @@ int open_plan_combine(OpenPlan& p, uint64_t len, uint32_t n_cols, const uint32_t
       snprintf(msg, msg_len, "term %u names column %u of %u", j, h_col[j], n_cols);
       return B2F_ERR_ARG;
     }
-    if (!canonical(form, h_scalar + 4ull * j)) {
+    if (!fe_canonical(form, h_scalar + 4ull * j)) {
       snprintf(msg, msg_len, "scalar %u is >= p", j);
       return B2F_ERR_ARG;
     }
@@ -497,9 +484,6 @@ hipError_t launch_poly_combine(const OpenPlan& p, const uint64_t* d_cols, uint64
                                void* d_scratch, uint64_t* d_out, uint64_t out_rows, hipStream_t s) {
   const uint64_t* blob = static_cast<const uint64_t*>(d_blob);
   uint64_t* scal = static_cast<uint64_t*>(d_scratch);
-  if (p.nnz)
-    OPEN_LAUNCH(p.form, scalar_prep_kernel, dim3((p.nnz + OP_THREADS - 1) / OP_THREADS), dim3(OP_THREADS), s,
-                blob + p.off_points, scal, p.nnz);
   CombineArgs a;
   a.cols = d_cols;
   a.rows = rows;
@@ -511,7 +495,13 @@ hipError_t launch_poly_combine(const OpenPlan& p, const uint64_t* d_cols, uint64
   a.out_rows = out_rows;
   a.n_out = p.n_out;
   const dim3 grid((uint32_t)((p.len + OP_THREADS - 1) / OP_THREADS), p.n_out < OP_MAX_Y ? p.n_out : OP_MAX_Y);
-  OPEN_LAUNCH(p.form, poly_combine_kernel, grid, dim3(OP_THREADS), s, a);
+  with_field(p.form, [&](auto f) {
+    using F = decltype(f);
+    if (p.nnz)
+      hipLaunchKernelGGL(scalar_prep_kernel<F>, dim3((p.nnz + OP_THREADS - 1) / OP_THREADS), dim3(OP_THREADS), 0, s,
+                         blob + p.off_points, scal, p.nnz);
+    hipLaunchKernelGGL(poly_combine_kernel<F>, grid, dim3(OP_THREADS), 0, s, a);
+  });
   return hipGetLastError();
 }
 
@@ -529,7 +519,7 @@ int open_plan_kate(OpenPlan& p, uint64_t len, uint32_t n_cols, const uint32_t* h
     }
   const uint32_t np = h_first[n_cols];
   for (uint32_t i = 0; i < np; i++)
-    if (!canonical(form, h_points + 4ull * i)) {
+    if (!fe_canonical(form, h_points + 4ull * i)) {
       snprintf(msg, msg_len, "point %u is >= p", i);
       return B2F_ERR_ARG;
     }
@@ -587,18 +577,21 @@ hipError_t launch_kate_divide(const OpenPlan& p, const uint64_t* d_cols, uint64_
     hipLaunchKernelGGL(kate_special_kernel, dim3(row_blocks, sn), dim3(OP_THREADS), 0, s, b);
   }
   if (p.passes) launch_pow_table(p, blob, tab, s);
-  for (uint32_t pass = 0; pass < p.passes; pass++) {
-    const uint32_t act = p.active[pass];
-    for (uint32_t s0 = 0; s0 < act; s0 += OP_MAX_Y) {
-      const uint32_t sn = act - s0 < OP_MAX_Y ? act - s0 : OP_MAX_Y;
-      OPEN_LAUNCH(p.form, kate_partial_kernel, dim3((uint32_t)p.ntiles, sn), dim3(OP_THREADS), s, a, s0, pass);
+  with_field(p.form, [&](auto f) {
+    using F = decltype(f);
+    for (uint32_t pass = 0; pass < p.passes; pass++) {
+      const uint32_t act = p.active[pass];
+      for (uint32_t s0 = 0; s0 < act; s0 += OP_MAX_Y) {
+        const uint32_t sn = act - s0 < OP_MAX_Y ? act - s0 : OP_MAX_Y;
+        hipLaunchKernelGGL(kate_partial_kernel<F>, dim3((uint32_t)p.ntiles, sn), dim3(OP_THREADS), 0, s, a, s0, pass);
+      }
+      hipLaunchKernelGGL(kate_scan_kernel<F>, dim3(act), dim3(64), 0, s, a, pass);
+      for (uint32_t s0 = 0; s0 < act; s0 += OP_MAX_Y) {
+        const uint32_t sn = act - s0 < OP_MAX_Y ? act - s0 : OP_MAX_Y;
+        hipLaunchKernelGGL(kate_apply_kernel<F>, dim3((uint32_t)p.ntiles, sn), dim3(OP_THREADS), 0, s, a, s0, pass);
+      }
     }
-    OPEN_LAUNCH(p.form, kate_scan_kernel, dim3(act), dim3(64), s, a, pass);
-    for (uint32_t s0 = 0; s0 < act; s0 += OP_MAX_Y) {
-      const uint32_t sn = act - s0 < OP_MAX_Y ? act - s0 : OP_MAX_Y;
-      OPEN_LAUNCH(p.form, kate_apply_kernel, dim3((uint32_t)p.ntiles, sn), dim3(OP_THREADS), s, a, s0, pass);
-    }
-  }
+  });
   return hipGetLastError();
 }
 

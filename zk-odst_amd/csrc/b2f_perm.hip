@@ -21,6 +21,7 @@
 #include "../../include/b2f.h"
 #include "b2f_field.h"
 #include "b2f_gprod.h"
+#include "b2f_launch.h"
 
 namespace b2f {
 
@@ -549,8 +550,9 @@ hipError_t launch_permutation_sigma(const uint64_t* d_inst, size_t n_inst, const
   I.pat = d_inst + n_inst + 1;
   I.n = (uint32_t)n_inst;
   const bool mont = (form & 1u) != 0;
-  if (form >> 1) return run_perm_sigma<field::Bn254>(I, d_pool, k, prm, mont, d_sigma, out_rows, scratch, s);
-  return run_perm_sigma<field::Pallas>(I, d_pool, k, prm, mont, d_sigma, out_rows, scratch, s);
+  return field::with_field(form, [&](auto f) {
+    return run_perm_sigma<decltype(f)>(I, d_pool, k, prm, mont, d_sigma, out_rows, scratch, s);
+  });
 }
 
 size_t perm_scratch_bytes(uint32_t k, uint64_t usable_rows, size_t, uint32_t chunk_len) {
@@ -578,11 +580,10 @@ hipError_t launch_permutation(const uint32_t* d_advice, uint64_t total_rows, uin
   I.pat = d_inst + n_inst + 1;
   I.n = (uint32_t)n_inst;
   const bool mont = (form & 1u) != 0;
-  if (form >> 1)
-    return run_perm<field::Bn254>(d_advice, total_rows, row0, I, d_pool, k, usable_rows, prm, gamma,
-                                  chunk_len, mont, d_sigma, d_z, out_rows, scratch, sticky, side, s);
-  return run_perm<field::Pallas>(d_advice, total_rows, row0, I, d_pool, k, usable_rows, prm, gamma,
-                                 chunk_len, mont, d_sigma, d_z, out_rows, scratch, sticky, side, s);
+  return field::with_field(form, [&](auto f) {
+    return run_perm<decltype(f)>(d_advice, total_rows, row0, I, d_pool, k, usable_rows, prm, gamma, chunk_len,
+                                 mont, d_sigma, d_z, out_rows, scratch, sticky, side, s);
+  });
 }
 
 // circuits per pass of the batch call: the lookup call's rule (at most 2^24 rows, enough
@@ -620,13 +621,10 @@ hipError_t launch_permutation_batch(const uint32_t* d_advice, uint64_t total_row
     prm.gamma[i] = gamma[i];
   }
   const bool mont = (form & 1u) != 0;
-  if (form >> 1)
-    return run_perm_batch<field::Bn254>(d_advice, total_rows, d_tab, n_circuits, group, d_pool, k,
-                                        usable_rows, prm, chunk_len, mont, d_z, out_rows, scratch, sticky,
-                                        side, s);
-  return run_perm_batch<field::Pallas>(d_advice, total_rows, d_tab, n_circuits, group, d_pool, k,
-                                       usable_rows, prm, chunk_len, mont, d_z, out_rows, scratch, sticky,
-                                       side, s);
+  return field::with_field(form, [&](auto f) {
+    return run_perm_batch<decltype(f)>(d_advice, total_rows, d_tab, n_circuits, group, d_pool, k, usable_rows,
+                                       prm, chunk_len, mont, d_z, out_rows, scratch, sticky, side, s);
+  });
 }
 
 }  // namespace b2f

@@ -23,6 +23,7 @@
 
 #include "../../include/b2f.h"
 #include "b2f_field.h"
+#include "b2f_launch.h"
 
 namespace b2f {
 
@@ -36,10 +37,6 @@ constexpr uint32_t QT_THREADS = 256;
 //   [0]  header: word 0 != 0 when omega is not a primitive 2^ext_k-th root of unity
 //   then T0[a] = shift omega^a (a < 2^h0), T1[b] = omega^(b 2^h0) (b < 2^(ext_k - h0))
 constexpr uint32_t QT_T0_OFF = 1;
-
-struct Words4 {
-  uint64_t v[4];
-};
 
 // the challenges of one call, Montgomery form
 struct QuotConsts {
@@ -488,23 +485,15 @@ __global__ __launch_bounds__(QT_THREADS) void quot_divide_kernel(const uint64_t*
   store(h_out + 4ull * i, mul<F>(load(h_in + 4ull * i), load(dtab + 4ull * (1 + (i & (rot - 1u))))));
 }
 
-Words4 words4(const uint64_t* v) {
-  Words4 w;
-  for (int i = 0; i < 4; i++) w.v[i] = v[i];
-  return w;
-}
-
 dim3 row_grid(uint32_t log_rows) { return dim3(((1u << log_rows) + QT_THREADS - 1) / QT_THREADS); }
 
 void launch_consts(uint32_t form, void* d_consts, const uint64_t* beta, const uint64_t* gamma, const uint64_t* y,
                    const uint64_t* delta, uint32_t sets, hipStream_t s) {
   QuotConsts* c = static_cast<QuotConsts*>(d_consts);
-  if ((form >> 1) & 1u)
-    hipLaunchKernelGGL(quot_consts_kernel<Bn254>, dim3(1), dim3(64), 0, s, c, words4(beta), words4(gamma),
+  with_field(form, [&](auto f) {
+    hipLaunchKernelGGL(quot_consts_kernel<decltype(f)>, dim3(1), dim3(64), 0, s, c, words4(beta), words4(gamma),
                        words4(y), words4(delta), sets);
-  else
-    hipLaunchKernelGGL(quot_consts_kernel<Pallas>, dim3(1), dim3(64), 0, s, c, words4(beta), words4(gamma),
-                       words4(y), words4(delta), sets);
+  });
 }
 
 }  // namespace
@@ -543,21 +532,19 @@ hipError_t launch_quot_xtab(void* d_tab, uint32_t form, uint32_t ext_k, const ui
   const uint32_t total = (1u << h0) + (1u << (ext_k - h0));
   const dim3 grid((total + QT_THREADS - 1) / QT_THREADS);
   uint64_t* tab = static_cast<uint64_t*>(d_tab);
-  if ((form >> 1) & 1u)
-    hipLaunchKernelGGL(quot_xtab_kernel<Bn254>, grid, dim3(QT_THREADS), 0, s, tab, words4(omega), words4(shift), ext_k);
-  else
-    hipLaunchKernelGGL(quot_xtab_kernel<Pallas>, grid, dim3(QT_THREADS), 0, s, tab, words4(omega), words4(shift), ext_k);
+  with_field(form, [&](auto f) {
+    hipLaunchKernelGGL(quot_xtab_kernel<decltype(f)>, grid, dim3(QT_THREADS), 0, s, tab, words4(omega), words4(shift),
+                       ext_k);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_lagrange_selectors(uint32_t k, uint32_t usable_rows, uint32_t form, uint64_t* d_out,
                                      uint64_t out_rows, hipStream_t s) {
-  if ((form >> 1) & 1u)
-    hipLaunchKernelGGL(quot_selectors_kernel<Bn254>, row_grid(k), dim3(QT_THREADS), 0, s, d_out, out_rows,
+  with_field(form, [&](auto f) {
+    hipLaunchKernelGGL(quot_selectors_kernel<decltype(f)>, row_grid(k), dim3(QT_THREADS), 0, s, d_out, out_rows,
                        1u << k, usable_rows, form & 1u);
-  else
-    hipLaunchKernelGGL(quot_selectors_kernel<Pallas>, row_grid(k), dim3(QT_THREADS), 0, s, d_out, out_rows,
-                       1u << k, usable_rows, form & 1u);
+  });
   return hipGetLastError();
 }
 
@@ -586,19 +573,9 @@ hipError_t launch_quot_permutation(uint32_t k, uint32_t ext_k, uint32_t usable_r
   a.colmap = colmap;
   launch_consts(form, d_consts, beta, gamma, y, delta, a.sets, s);
   const dim3 block(QT_THREADS), grid = row_grid(ext_k);
-  switch (form) {
-    case B2F_FP_CANONICAL:
-      hipLaunchKernelGGL((quot_perm_kernel<Pallas, false>), grid, block, 0, s, a);
-      break;
-    case B2F_FP_MONTGOMERY:
-      hipLaunchKernelGGL((quot_perm_kernel<Pallas, true>), grid, block, 0, s, a);
-      break;
-    case B2F_FP_BN254_CANONICAL:
-      hipLaunchKernelGGL((quot_perm_kernel<Bn254, false>), grid, block, 0, s, a);
-      break;
-    default:
-      hipLaunchKernelGGL((quot_perm_kernel<Bn254, true>), grid, block, 0, s, a);
-  }
+  with_form(form, [&](auto f, auto mont) {
+    hipLaunchKernelGGL((quot_perm_kernel<decltype(f), decltype(mont)::value>), grid, block, 0, s, a);
+  });
   return hipGetLastError();
 }
 
@@ -618,19 +595,9 @@ hipError_t launch_quot_lookup(uint32_t k, uint32_t ext_k, const uint64_t* d_l, c
   const uint64_t one_w[4] = {1, 0, 0, 0};  // delta: the lookup has no identity columns
   launch_consts(form, d_consts, beta, gamma, y, one_w, 0, s);
   const dim3 block(QT_THREADS), grid = row_grid(ext_k);
-  switch (form) {
-    case B2F_FP_CANONICAL:
-      hipLaunchKernelGGL((quot_lookup_kernel<Pallas, false>), grid, block, 0, s, a);
-      break;
-    case B2F_FP_MONTGOMERY:
-      hipLaunchKernelGGL((quot_lookup_kernel<Pallas, true>), grid, block, 0, s, a);
-      break;
-    case B2F_FP_BN254_CANONICAL:
-      hipLaunchKernelGGL((quot_lookup_kernel<Bn254, false>), grid, block, 0, s, a);
-      break;
-    default:
-      hipLaunchKernelGGL((quot_lookup_kernel<Bn254, true>), grid, block, 0, s, a);
-  }
+  with_form(form, [&](auto f, auto mont) {
+    hipLaunchKernelGGL((quot_lookup_kernel<decltype(f), decltype(mont)::value>), grid, block, 0, s, a);
+  });
   return hipGetLastError();
 }
 
@@ -647,24 +614,13 @@ hipError_t launch_quot_gates(uint32_t k, uint32_t ext_k, const uint64_t* d_advic
   a.ext_k = ext_k;
   a.rot = 1u << (ext_k - k);
   GateConsts* c = static_cast<GateConsts*>(d_consts);
-  if ((form >> 1) & 1u)
-    hipLaunchKernelGGL(quot_gate_consts_kernel<Bn254>, dim3(1), dim3(64), 0, s, c, words4(y));
-  else
-    hipLaunchKernelGGL(quot_gate_consts_kernel<Pallas>, dim3(1), dim3(64), 0, s, c, words4(y));
+  with_field(form, [&](auto f) {
+    hipLaunchKernelGGL(quot_gate_consts_kernel<decltype(f)>, dim3(1), dim3(64), 0, s, c, words4(y));
+  });
   const dim3 block(QT_THREADS), grid = row_grid(ext_k);
-  switch (form) {
-    case B2F_FP_CANONICAL:
-      hipLaunchKernelGGL((quot_gates_kernel<Pallas, false>), grid, block, 0, s, a);
-      break;
-    case B2F_FP_MONTGOMERY:
-      hipLaunchKernelGGL((quot_gates_kernel<Pallas, true>), grid, block, 0, s, a);
-      break;
-    case B2F_FP_BN254_CANONICAL:
-      hipLaunchKernelGGL((quot_gates_kernel<Bn254, false>), grid, block, 0, s, a);
-      break;
-    default:
-      hipLaunchKernelGGL((quot_gates_kernel<Bn254, true>), grid, block, 0, s, a);
-  }
+  with_form(form, [&](auto f, auto mont) {
+    hipLaunchKernelGGL((quot_gates_kernel<decltype(f), decltype(mont)::value>), grid, block, 0, s, a);
+  });
   return hipGetLastError();
 }
 
@@ -677,10 +633,10 @@ hipError_t launch_quot_divisors(void* d_dtab, uint32_t form, uint32_t k, uint32_
   const hipError_t e = hipMemsetAsync(dtab, 0, 32, s);
   if (e != hipSuccess) return e;
   const dim3 block(QT_THREADS), grid = row_grid(ext_k - k);
-  if ((form >> 1) & 1u)
-    hipLaunchKernelGGL(quot_divisor_kernel<Bn254>, grid, block, 0, s, dtab, words4(omega), words4(shift), k, ext_k);
-  else
-    hipLaunchKernelGGL(quot_divisor_kernel<Pallas>, grid, block, 0, s, dtab, words4(omega), words4(shift), k, ext_k);
+  with_field(form, [&](auto f) {
+    hipLaunchKernelGGL(quot_divisor_kernel<decltype(f)>, grid, block, 0, s, dtab, words4(omega), words4(shift), k,
+                       ext_k);
+  });
   return hipGetLastError();
 }
 
@@ -688,12 +644,10 @@ hipError_t launch_quot_divide(uint32_t k, uint32_t ext_k, const uint64_t* d_h_in
                               uint32_t form, const void* d_dtab, int* sticky, hipStream_t s) {
   const uint64_t* dtab = static_cast<const uint64_t*>(d_dtab);
   const uint32_t rot = 1u << (ext_k - k);
-  if ((form >> 1) & 1u)
-    hipLaunchKernelGGL(quot_divide_kernel<Bn254>, row_grid(ext_k), dim3(QT_THREADS), 0, s, d_h_in, d_h_out, dtab,
-                       ext_k, rot, sticky);
-  else
-    hipLaunchKernelGGL(quot_divide_kernel<Pallas>, row_grid(ext_k), dim3(QT_THREADS), 0, s, d_h_in, d_h_out, dtab,
-                       ext_k, rot, sticky);
+  with_field(form, [&](auto f) {
+    hipLaunchKernelGGL(quot_divide_kernel<decltype(f)>, row_grid(ext_k), dim3(QT_THREADS), 0, s, d_h_in, d_h_out,
+                       dtab, ext_k, rot, sticky);
+  });
   return hipGetLastError();
 }
 
