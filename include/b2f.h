@@ -558,6 +558,40 @@ B2F_API int b2f_kate_divide_dev(b2f_ctx* ctx, const uint64_t* d_cols, uint64_t r
                                 uint32_t n_cols, const uint32_t* h_first, const uint64_t* h_points,
                                 uint32_t form, uint64_t* d_out, uint64_t out_rows, void* stream);
 
+/* The commitments: a batched variable-base multi-scalar multiplication on the curve whose scalar
+ * field `form` names: Vesta (y^2 = x^3 + 5 over pasta Fq, group order pasta Fp) for forms 0/1,
+ * BN254 G1 (y^2 = x^3 + 3 over bn256::Fq, group order bn256::Fr) for forms 2/3. This is halo2's
+ * commit / commit_lagrange of a column against the parameters' points (g, g_lagrange); building
+ * those points, the blinding term's generator, the transcript and the IPA / KZG opening stay with
+ * the caller.
+ * d_scalars is a column block d[(c * rows + i) * 4 + limb] in `form` (any B2F_FP_*, reduced: the
+ * blocks every other prover call produces); rows >= len are never read. d_bases holds n_bases >=
+ * len affine points shared by all columns, a point being (x, y), each coordinate four
+ * little-endian u64 limbs in base-field Montgomery form (R = 2^256), 64 bytes, the identity all
+ * zero: d_bases[i * 8 + 0..3] = x, [i * 8 + 4..7] = y. A (0, 0) base contributes nothing. Points
+ * are NOT checked to be on the curve: off-curve input gives a meaningless point and never an
+ * out-of-range access. d_out receives n_cols affine points in the same layout, d_out[c * 8 + ..],
+ * the identity as all zeros; the affine form is canonical, so the result is bit-exact whatever
+ * the order of summation.
+ * Pippenger's bucket method: signed c-bit digits, a radix sort by (column, window, bucket), bucket
+ * sums by a levelled reduction in which no lane adds more than 32 points in a row whatever the
+ * scalars' distribution, window sums by running sums, Horner over the windows and one inversion
+ * per output (B2F_ERR_CHECK at b2f_sync if that inversion fails: a library defect). Columns and
+ * rows are processed in passes of at most 2^24 digits and 2^20 buckets, so scratch (the context's)
+ * is bounded: b2f_msm_plan reports it. Asynchronous on `stream`; pointers are 16-byte aligned; one
+ * B2F_KERNEL_QUOTIENT region per call. Errors, nothing launched and the next good call works:
+ * B2F_ERR_ARG for a null or misaligned pointer, form > 3, len == 0 or len > 2^28, n_cols == 0,
+ * d_out overlapping an input; B2F_ERR_ROWS for len > rows or len > n_bases; B2F_ERR_HIP for
+ * runtime failures, scratch growth included. */
+/* out[c] = sum_{i < len} scalar[c][i] * base[i], c < n_cols */
+B2F_API int b2f_msm_dev(b2f_ctx* ctx, const uint64_t* d_scalars, uint64_t rows, uint64_t len,
+                        uint32_t n_cols, const uint64_t* d_bases, uint64_t n_bases, uint32_t form,
+                        uint64_t* d_out, void* stream);
+/* host only: the plan b2f_msm_dev would use (window bits, windows, columns per group, scratch bytes);
+ * B2F_ERR_ARG where the call would refuse len, n_cols or form. Any output pointer may be null. */
+B2F_API int b2f_msm_plan(uint64_t len, uint32_t n_cols, uint32_t form, uint32_t* window_bits,
+                         uint32_t* windows, uint32_t* group, uint64_t* scratch_bytes);
+
 /* The advice queries of the chip: the (halo2 advice column, rotation) pairs the sixteen gates read
  * (the list at b2f_quotient_gates_dev), as a set, sorted by column then rotation; writes
  * min(count, cap) pairs (column, rotation) and returns count. These are the evaluations of advice
@@ -582,7 +616,7 @@ B2F_API uint64_t b2f_gate_queries(uint32_t* pairs, uint64_t cap);
 #define B2F_KERNEL_PERM_SIGMA 7 /* permutation keygen: the sigma columns (b2f_permutation_sigma_dev) */
 #define B2F_KERNEL_NTT 8    /* NTT of prover columns (table build and all passes of one call) */
 #define B2F_KERNEL_QUOTIENT 9 /* quotient terms, the vanishing divide, the Lagrange selectors and the
-                                 evaluation / opening calls */
+                                 evaluation / opening calls; the commitments (b2f_msm_dev) */
 #define B2F_NUM_KERNELS 10
 /* total_ms and count must each hold b2f_num_kernels() entries (= B2F_NUM_KERNELS of the
  * header the library was built with; it grew from 7 to 8 with B2F_KERNEL_PERM_SIGMA, to 9

@@ -22,6 +22,9 @@ Scheme (product scanning, 8 x 32-bit words, R = 2^256):
 The result is < 2p (both moduli have a top word below 2^31 - 1) and reduce_once_asm finishes it
 by a borrow chain and v_cndmask.
 
+Four fields are emitted: the scalar fields Pallas and Bn254, and the base fields of the commitment
+curves, VestaBase (the same shape as pallas: the shortcuts apply) and Bn254Base.
+
 Run: python tools/gen_mont_asm.py  (writes the header; tests/test_mont_asm_gen.py checks the
 committed header is what this script writes).
 """
@@ -33,6 +36,13 @@ PALLAS_NP = 0xffffffff
 BN254_P = [0xf0000001, 0x43e1f593, 0x79b97091, 0x2833e848, 0x8181585d, 0xb85045b6, 0xe131a029,
            0x30644e72]
 BN254_NP = 0xefffffff
+# the base fields of the commitment curves (b2f_curve.h): Vesta's (pasta Fq, the same shape as
+# pallas Fp above, so product_asm's pallas shortcuts apply to it) and BN254 G1's (bn256::Fq)
+VESTA_BASE_P = [0x00000001, 0x8c46eb21, 0x0994a8dd, 0x224698fc, 0, 0, 0, 0x40000000]
+VESTA_BASE_NP = 0xffffffff
+BN254_BASE_P = [0xd87cfd47, 0x3c208c16, 0x6871ca8d, 0x97816a91, 0x8181585d, 0xb85045b6, 0xe131a029,
+                0x30644e72]
+BN254_BASE_NP = 0xe4866389
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                    "zk-odst_amd", "csrc", "b2f_mont_asm.h")
@@ -220,6 +230,10 @@ def generate():
     hdr += emit("Pallas", PALLAS_P, PALLAS_NP)
     hdr.append("")
     hdr += emit("Bn254", BN254_P, BN254_NP)
+    hdr.append("")
+    hdr += emit("VestaBase", VESTA_BASE_P, VESTA_BASE_NP)
+    hdr.append("")
+    hdr += emit("Bn254Base", BN254_BASE_P, BN254_BASE_NP)
     return "\n".join(hdr) + "\n"
 
 

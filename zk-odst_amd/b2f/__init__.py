@@ -9,4 +9,4 @@ from .layout import (INPUT_DTYPE, SELECTORS, as_inputs, halo2_column_index, offs
                      parse_eip152, rows, split_fixed)
 from .engine import (DeviceBatch, Engine, copy_constraints, gate_queries,  # noqa: F401
                      permutation_mapping)
-from . import field  # noqa: F401
+from . import curve, field  # noqa: F401

@@ -132,6 +132,8 @@ SIGNATURES = [
     ("b2f_poly_combine_dev", I32, [P, P, U64, U64, ctypes.c_uint32, P, P, P, ctypes.c_uint32,
                                    ctypes.c_uint32, P, U64, P]),
     ("b2f_kate_divide_dev", I32, [P, P, U64, U64, ctypes.c_uint32, P, P, ctypes.c_uint32, P, U64, P]),
+    ("b2f_msm_dev", I32, [P, P, U64, U64, ctypes.c_uint32, P, U64, ctypes.c_uint32, P, P]),
+    ("b2f_msm_plan", I32, [U64, ctypes.c_uint32, ctypes.c_uint32, P, P, P, P]),
     ("b2f_gate_queries", U64, [P, U64]),
     ("b2f_sync", I32, [P, P]),
     ("b2f_fill", I32, [P, P, SIZE, P, P, P]),
@@ -145,10 +147,17 @@ SIGNATURES = [
 DIAG_SIGNATURES = [
     ("b2f_debug_field_op", I32, [ctypes.c_uint32, ctypes.c_uint32, P, P, SIZE, P, P]),
     ("b2f_debug_ntt_plan", I32, [ctypes.c_uint32, P]),
+    ("b2f_debug_curve_op", I32, [ctypes.c_uint32, ctypes.c_uint32, P, P, P, P, SIZE, P, P]),
 ]
 # op codes of b2f_debug_field_op (csrc/b2f_fieldprobe.hip)
 FIELD_OPS = ["mul", "mul_comba", "mul_cios", "add", "sub", "from_u32", "to_mont", "to_canonical",
              "fe_pow", "inv", "inv_kaliski", "inv_safegcd", "inv_fermat"]
+
+# op codes of b2f_debug_curve_op (csrc/b2f_curveprobe.hip): the first CURVE_FIELD_OPS are
+# base-field primitives (four-limb operands), the rest point operations (eight-limb points)
+CURVE_OPS = ["mul", "add", "sub", "to_mont", "to_canonical", "inv_safegcd",
+             "madd", "padd", "dbl", "neg", "mdbl"]
+CURVE_FIELD_OPS = 6
 
 _libs = {}
 
@@ -203,6 +212,20 @@ def debug_ntt_plan(k):
         raise B2FError(rc, "no pass plan for k = %d under B2F_DIAG_NTT_PLAN=%r"
                        % (k, os.environ.get("B2F_DIAG_NTT_PLAN")))
     return [int(v) for v in out[1:1 + out[0]]]
+
+
+def msm_plan(len_, n_cols, form=FP_MONTGOMERY, diag=False):
+    """Host only (b2f_msm_plan): the plan b2f_msm_dev would run, as a dict of window_bits, windows,
+    group (columns per pass) and scratch_bytes. diag=True asks the diagnostics library, which
+    honours B2F_DIAG_MSM_PLAN=c[,g]. B2FError(ERR_ARG) where the call would be refused."""
+    c, w, g = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+    sb = ctypes.c_uint64(0)
+    rc = load(diag=diag).b2f_msm_plan(int(len_), int(n_cols), int(form), ctypes.byref(c), ctypes.byref(w),
+                                      ctypes.byref(g), ctypes.byref(sb))
+    if rc != OK:
+        raise B2FError(rc, "no msm plan for len = %d, n_cols = %d, form = %d" % (len_, n_cols, form))
+    return {"window_bits": int(c.value), "windows": int(w.value), "group": int(g.value),
+            "scratch_bytes": int(sb.value)}
 
 
 def check(ctx, rc, lib=None):

@@ -518,6 +518,60 @@ class Engine:
         self.kate_divide_dev(cols.data_ptr(), rows, n, n_cols, point_lists, form, out.data_ptr(), out_rows, s)
         return out
 
+    # ---------------------------------------------------------------- commitments
+    def msm_dev(self, d_scalars, rows, len_, n_cols, d_bases, n_bases, form, d_out, stream=0):
+        """b2f_msm_dev: d_out[c] = sum_i scalar[c][i] base[i] for n_cols columns, as affine points
+        in base-field Montgomery form (b2f/curve.py packs and unpacks them)."""
+        self._check(self.lib.b2f_msm_dev(self.ctx, _vp(d_scalars), int(rows), int(len_), int(n_cols),
+                                         _vp(d_bases), int(n_bases), int(form), _vp(d_out), _vp(stream)))
+
+    def msm(self, scalars, bases, len=None, form=_lib.FP_MONTGOMERY, out=None, stream=None):
+        """Commitments of columns (b2f_msm_dev). scalars: int64 [n_cols, rows, 4] in `form`, the
+        first `len` rows (default: all) of each committed; bases: int64 [n_bases >= len, 8] affine
+        points of the form's curve (curve.pack_points). Returns int64 [n_cols, 8] affine points, the
+        identity all zeros."""
+        import torch
+
+        n_cols, rows = self._coeff_cols("msm: scalars", scalars)
+        n = rows if len is None else int(len)
+        if bases.dim() != 2 or bases.shape[1] != 8 or bases.dtype != torch.int64 or not bases.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "msm: bases must be contiguous int64 [n_bases, 8]")
+        if out is None:
+            out = torch.empty((n_cols, 8), dtype=torch.int64, device=scalars.device)
+        if out.dim() != 2 or tuple(out.shape) != (n_cols, 8) or out.dtype != torch.int64 or not out.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "msm: out must be contiguous int64 [n_cols, 8]")
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.msm_dev(scalars.data_ptr(), rows, n, n_cols, bases.data_ptr(), int(bases.shape[0]), form,
+                     out.data_ptr(), s)
+        return out
+
+    def debug_curve_op(self, op, a, b, curve, za=None, zb=None):
+        """Diagnostics build only (b2f_debug_curve_op): the base-field primitive or point operation
+        `op` (a name of _lib.CURVE_OPS) on the device, one lane per element. Field ops: a, b uint64
+        [n, 4]; point ops: a, b uint64 [n, 8] affine points and za, zb uint64 [n, 4] the z the
+        operand is lifted to XYZZ with. curve: 0 Vesta, 1 BN254 G1. Returns (out, flags uint32 [n])."""
+        idx = _lib.CURVE_OPS.index(op)
+        w = 4 if idx < _lib.CURVE_FIELD_OPS else 8
+        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, w)
+        b = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, w)
+        if len(a) != len(b):
+            raise _lib.B2FError(_lib.ERR_ARG, "debug_curve_op: a and b differ in length")
+        zs = []
+        for z in (za, zb):
+            if z is None:
+                z = np.zeros((len(a), 4), dtype=np.uint64)
+            z = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4)
+            if len(z) != len(a):
+                raise _lib.B2FError(_lib.ERR_ARG, "debug_curve_op: z differs in length")
+            zs.append(z)
+        out = np.zeros_like(a)
+        flags = np.zeros(len(a), dtype=np.uint32)
+        rc = self.lib.b2f_debug_curve_op(int(curve), idx, _np_ptr(a), _np_ptr(b), _np_ptr(zs[0]),
+                                         _np_ptr(zs[1]), len(a), _np_ptr(out), _np_ptr(flags))
+        if rc != _lib.OK:
+            raise _lib.B2FError(rc, "debug_curve_op(%s) refused or failed" % op)
+        return out, flags
+
     def debug_eval_path(self):
         """Path of the last eval_dev call (device-synchronizing): 0 the fast clean-check pass
         found the trace clean, 1 it flagged something and the exact eval kernel reported, 2 no

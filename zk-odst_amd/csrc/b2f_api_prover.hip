@@ -1,5 +1,5 @@
 // b2f_api_prover.hip -- the C ABI of the prover calls of include/b2f.h: column export, the lookup,
-// permutation, NTT, quotient and opening steps. Host code only: argument checks, the context's
+// permutation, NTT, quotient and opening steps, the commitments. Host code only: argument checks, the context's
 // scratch and table blocks, and the launchers of b2f_launch.h / b2f_open.h. The trace calls, the
 // context itself and keygen are in b2f_kernels.hip.
 #include <hip/hip_runtime.h>
@@ -732,6 +732,64 @@ B2F_API int b2f_kate_divide_dev(b2f_ctx* ctx, const uint64_t* d_cols, uint64_t r
   if (int rc = open_upload(ctx, plan, s)) return rc;
   int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
   HIPCHK(ctx, launch_kate_divide(plan, d_cols, rows, ctx->d_op_blob, ctx->d_op, d_out, out_rows, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// The plan of a commitment call: the product's, or under the diagnostics library the one
+// B2F_DIAG_MSM_PLAN forces. false: the arguments (or the forced plan) are refused.
+bool msm_plan_for(uint64_t len, uint32_t n_cols, uint32_t form, MsmPlan* plan) {
+  if (form > B2F_FP_BN254_MONTGOMERY) return false;
+  uint32_t fc = 0, fg = 0;
+#ifdef B2F_DIAG
+  if (diag_msm_plan(&fc, &fg) < 0) return false;
+#endif
+  return msm_plan_of(len, n_cols, fc, fg, plan);
+}
+}  // namespace
+
+extern "C" {
+
+B2F_API int b2f_msm_plan(uint64_t len, uint32_t n_cols, uint32_t form, uint32_t* window_bits,
+                         uint32_t* windows, uint32_t* group, uint64_t* scratch_bytes) {
+  MsmPlan plan;
+  if (!msm_plan_for(len, n_cols, form, &plan)) return B2F_ERR_ARG;
+  if (window_bits) *window_bits = plan.c;
+  if (windows) *windows = plan.windows;
+  if (group) *group = plan.group;
+  if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+  return B2F_OK;
+}
+
+B2F_API int b2f_msm_dev(b2f_ctx* ctx, const uint64_t* d_scalars, uint64_t rows, uint64_t len,
+                        uint32_t n_cols, const uint64_t* d_bases, uint64_t n_bases, uint32_t form,
+                        uint64_t* d_out, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "msm";
+  if (!d_scalars || !d_bases || !d_out) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (((uintptr_t)d_scalars | (uintptr_t)d_bases | (uintptr_t)d_out) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "%s: buffers must be 16-byte aligned", what);
+  if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "%s: unknown form %u", what, form);
+  if (len == 0 || n_cols == 0) return set_err(ctx, B2F_ERR_ARG, "%s: no columns or no scalars", what);
+  if (len > (1ull << 28)) return set_err(ctx, B2F_ERR_ARG, "%s: len %llu > 2^28", what, (unsigned long long)len);
+  if (len > rows) return set_err(ctx, B2F_ERR_ROWS, "%s: len %llu > rows", what, (unsigned long long)len);
+  if (len > n_bases) return set_err(ctx, B2F_ERR_ROWS, "%s: len %llu > n_bases", what, (unsigned long long)len);
+  if (rows > (1ull << 58) / n_cols || n_bases > (1ull << 57))
+    return set_err(ctx, B2F_ERR_ARG, "%s: column stride overflows the address space", what);
+  if (ranges_overlap(d_out, 64ull * n_cols, d_scalars, (uint64_t)n_cols * rows * 32) ||
+      ranges_overlap(d_out, 64ull * n_cols, d_bases, n_bases * 64))
+    return set_err(ctx, B2F_ERR_ARG, "%s: the output overlaps an input", what);
+  MsmPlan plan;
+  if (!msm_plan_for(len, n_cols, form, &plan))
+    return set_err(ctx, B2F_ERR_ARG, "%s: no plan (a forced plan that is malformed or exceeds a pass)", what);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = grow_device(ctx, &ctx->d_msm, &ctx->msm_cap, plan.scratch_bytes, 1, s)) return rc;
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_msm(plan, d_scalars, rows, len, n_cols, d_bases, form, d_out, ctx->d_msm, ctx->d_status + 2, s));
   timed_end(ctx, tk, s);
   return B2F_OK;
 }

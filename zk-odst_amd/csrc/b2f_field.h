@@ -1,4 +1,5 @@
-// b2f_field.h -- the prime fields of the prover columns, on the device.
+// b2f_field.h -- the prime fields of the prover columns, on the device (and, further down, the
+// base fields of the two commitment curves, which the same templates serve).
 //
 //   Pallas: pallas::Base = pasta_curves 0.5.1 Fp (Cargo.lock:1334-1337), the field of
 //           halo2_proofs 0.3.0's own tests;
@@ -54,7 +55,54 @@ struct Bn254 {
   static constexpr uint64_t RQ = 0x4a47462623a04a7aull;
 };
 
+// The base fields of the commitment curves (b2f_curve.h, b2f_msm.hip): the coordinates of the
+// points a column is committed against. VestaBase is pasta Fq (Vesta's base field = Pallas' scalar
+// field), Bn254Base is bn256::Fq. The constants are computed from the moduli (R = 2^256 mod q,
+// R2 = R^2, R3 = R^3, NP = -q^-1 mod 2^32, RQ = floor(R 2^64 / q)); tests/test_msm_ref.py
+// recomputes them. VestaBase has pallas' shape (q_0 = 1, q_4..q_6 = 0, q_7 = 2^30, NP = -1), so
+// the generated product takes the same shortcuts.
+struct VestaBase {
+  static constexpr uint32_t P[8] = {0x00000001u, 0x8c46eb21u, 0x0994a8ddu, 0x224698fcu,
+                                    0x00000000u, 0x00000000u, 0x00000000u, 0x40000000u};
+  static constexpr uint32_t R[8] = {0xfffffffdu, 0x5b2b3e9cu, 0xe3420567u, 0x992c350bu,
+                                    0xffffffffu, 0xffffffffu, 0xffffffffu, 0x3fffffffu};
+  static constexpr uint32_t R2[8] = {0x0000000fu, 0xfc9678ffu, 0x891a16e3u, 0x67bb433du,
+                                     0x04ccf590u, 0x7fae2310u, 0x7ccfdaa9u, 0x096d41afu};
+  static constexpr uint32_t R3[8] = {0x249dae4cu, 0x008b421cu, 0xdba41326u, 0xe13bda50u,
+                                     0x8e15cb63u, 0x88fececbu, 0x6e6792c8u, 0x07dd97a0u};
+  static constexpr uint32_t NP = 0xffffffffu;
+  static constexpr uint64_t RQ = 0xffffffffffffffffull;
+};
+
+struct Bn254Base {
+  static constexpr uint32_t P[8] = {0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u,
+                                    0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
+  static constexpr uint32_t R[8] = {0xc58f0d9du, 0xd35d438du, 0xf5c70b3du, 0x0a78eb28u,
+                                    0x7879462cu, 0x666ea36fu, 0x9a07df2fu, 0x0e0a77c1u};
+  static constexpr uint32_t R2[8] = {0x538afa89u, 0xf32cfc5bu, 0xd44501fbu, 0xb5e71911u,
+                                     0x0a417ff6u, 0x47ab1effu, 0xcab8351fu, 0x06d89f71u};
+  static constexpr uint32_t R3[8] = {0xda1530dfu, 0xb1cd6dafu, 0xa7283db6u, 0x62f210e6u,
+                                     0x0ada0afbu, 0xef7f0b0cu, 0x2d592544u, 0x20fd6e90u};
+  static constexpr uint32_t NP = 0xe4866389u;
+  static constexpr uint64_t RQ = 0x4a47462623a04a7aull;
+};
+
 static_assert(Pallas::P[7] < 0x7ffffffeu && Bn254::P[7] < 0x7ffffffeu, "no-carry CIOS needs a spare top bit");
+static_assert(VestaBase::P[7] < 0x7ffffffeu && Bn254Base::P[7] < 0x7ffffffeu, "the base fields too");
+
+// The commitment curve of a form's scalar field: y^2 = x^3 + B over the base field Base, whose
+// group order is the modulus of Scalar. Forms 0/1: Vesta (y^2 = x^3 + 5, order pasta Fp);
+// forms 2/3: BN254 G1 (y^2 = x^3 + 3, order bn256::Fr).
+struct VestaCurve {
+  using Base = VestaBase;
+  using Scalar = Pallas;
+  static constexpr uint32_t B = 5;
+};
+struct Bn254G1 {
+  using Base = Bn254Base;
+  using Scalar = Bn254;
+  static constexpr uint32_t B = 3;
+};
 
 // Host-side dispatch on a B2F_FP_* form (bit 1: the field, bit 0: Montgomery form), for launching
 // kernel<F> or kernel<F, MONT>: with_field calls fn(Pallas{}) or fn(Bn254{}) and returns what it
@@ -69,6 +117,21 @@ void with_form(uint32_t form, Fn&& fn) {
   with_field(form, [&](auto f) {
     if (form & 1u) fn(f, std::true_type{});
     else fn(f, std::false_type{});
+  });
+}
+
+// with_field's sibling for the commitment calls: the curve of the form (its base field and the
+// constant b), fn(VestaCurve{}) or fn(Bn254G1{}); with_curve_form adds the scalars' MONT flag.
+template <class Fn>
+auto with_curve(uint32_t form, Fn&& fn) {
+  if ((form >> 1) & 1u) return fn(Bn254G1{});
+  return fn(VestaCurve{});
+}
+template <class Fn>
+void with_curve_form(uint32_t form, Fn&& fn) {
+  with_curve(form, [&](auto c) {
+    if (form & 1u) fn(c, std::true_type{});
+    else fn(c, std::false_type{});
   });
 }
 

@@ -80,6 +80,8 @@ struct b2f_ctx {
   size_t op_blob_cap;  // in u64 words
   void* d_op;
   size_t op_cap;
+  void* d_msm;  // commitment scratch (b2f_msm.hip: msm_plan_of carves it)
+  size_t msm_cap;
 };
 
 namespace b2f {

@@ -1168,6 +1168,7 @@ B2F_API void b2f_destroy(b2f_ctx* ctx) {
   (void)hipFree(ctx->d_quot_consts);
   (void)hipFree(ctx->d_op_blob);
   (void)hipFree(ctx->d_op);
+  (void)hipFree(ctx->d_msm);
   if (ctx->op_ev_live) (void)hipEventSynchronize(ctx->op_ev);
   if (ctx->op_ev) (void)hipEventDestroy(ctx->op_ev);
   (void)hipHostFree(ctx->h_op);

@@ -84,6 +84,26 @@ hipError_t launch_quot_divisors(void* d_dtab, uint32_t form, uint32_t k, uint32_
 hipError_t launch_quot_divide(uint32_t k, uint32_t ext_k, const uint64_t* d_h_in, uint64_t* d_h_out,
                               uint32_t form, const void* d_dtab, int* sticky, hipStream_t s);
 
+// b2f_msm.hip: the plan of a commitment call (host only; the one place its scratch is sized) and
+// the launcher. force_c / force_g: 0, or the diagnostics library's forced window width / group.
+struct MsmPlan {
+  uint32_t c, windows, buckets;  // window bits, windows per scalar, buckets per window (2^(c-1))
+  uint32_t group;                // columns per pass
+  uint64_t chunk;                // rows per pass
+  uint64_t cap_entries, cap_buckets;  // what the scratch holds: digits and buckets of one pass
+  uint64_t off_keys_a, off_keys_b, off_vals_a, off_vals_b, off_sort, sort_bytes, off_pkey_a, off_pkey_b,
+      off_ppt_a, off_ppt_b, off_buckets, off_win, off_acc;
+  uint64_t scratch_bytes;
+};
+uint32_t msm_default_window(uint64_t len);
+bool msm_plan_of(uint64_t len, uint32_t n_cols, uint32_t force_c, uint32_t force_g, MsmPlan* plan);
+hipError_t launch_msm(const MsmPlan& plan, const uint64_t* d_scalars, uint64_t rows, uint64_t len, uint32_t n_cols,
+                      const uint64_t* d_bases, uint32_t form, uint64_t* d_out, void* scratch, int* sticky,
+                      hipStream_t s);
+#ifdef B2F_DIAG
+int diag_msm_plan(uint32_t* c, uint32_t* g);
+#endif
+
 // b2f_export.hip
 hipError_t launch_export_fp(const uint32_t* d_advice, uint64_t total_rows, uint64_t row_begin,
                             uint64_t nrows, uint32_t form, uint64_t* d_out, uint64_t out_rows,
