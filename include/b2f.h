@@ -153,6 +153,34 @@ B2F_API int b2f_fill_eval_dev(b2f_ctx* ctx, const b2f_input* d_in, size_t n,
                               uint32_t* d_fixed, uint64_t* d_h_out, b2f_eval_report* d_report,
                               void* stream);
 
+/* b2f_fill_eval_dev with flags; flags = 0 is that call. The fixed column (selector mask and
+ * k_0) is a function of the row map alone -- keygen output, what b2f_fill_fixed_dev writes, no
+ * witness in it -- so a prover that runs many witnesses of one circuit shape through the same
+ * buffers need not write it again:
+ *   B2F_FIXED_RESIDENT  the caller states that d_fixed already holds this row map's column,
+ *                       written by an earlier fused call of `ctx` with the same d_fixed,
+ *                       d_offsets, n and total_rows, and that nothing has written it (or the row
+ *                       map) since. The call may then leave d_fixed unwritten: 40 instead of
+ *                       44 bytes stored per row. Advice, h' and report are what the full call
+ *                       gives; the fixed cells are still formed and checked on the CU.
+ * The library honours the flag only where its own record agrees: the context's last full fused
+ * write with the inject hook off (the call was issued without error, and no b2f_fill_dev,
+ * b2f_fill_fixed_dev or failing b2f_sync of this context came after it) had exactly these four
+ * arguments, and the hook is off. Otherwise the call silently runs in full and renews the record;
+ * under the hook it runs in full and clears it. The record knows nothing of writes made outside
+ * these calls: those are what the caller's statement covers. The diagnostics build ignores the
+ * flag. Unknown flag bits: B2F_ERR_ARG. Timed as B2F_KERNEL_FILL_EVAL. */
+#define B2F_FIXED_RESIDENT 1u
+B2F_API int b2f_fill_eval_dev_ex(b2f_ctx* ctx, const b2f_input* d_in, size_t n,
+                                 const uint64_t* d_offsets, uint64_t total_rows, uint32_t* d_advice,
+                                 uint32_t* d_fixed, uint64_t* d_h_out, b2f_eval_report* d_report,
+                                 uint32_t flags, void* stream);
+
+/* Test hook: which kernel the last b2f_fill_eval_dev[_ex] call of `ctx` launched: *out = 0 the
+ * full one (every column written), 1 the advice-only one (B2F_FIXED_RESIDENT honoured). Host
+ * state only: no synchronize. */
+B2F_API int b2f_debug_fused_path(b2f_ctx* ctx, uint32_t* out);
+
 /* Test hook for the fused path: XOR `mask` into cell (row, col) as b2f_fill_eval_dev assigns
  * it (col 0..9 = a_col, 10 = the fixed column), so both the trace it writes and the trace it
  * checks carry the fault; row = UINT64_MAX turns it off (the default). Lets tests prove the

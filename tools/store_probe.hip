@@ -8,6 +8,8 @@
 //           line-owned half-round tiles, the edge rows afterwards -- with the junction lines
 //           split as the fused pass wrote them, final | init paired, all written whole, or
 //           paired with only the first tile's line owned
+//           (store_probe <n> j <reps> 10) the whole-line order with 11 columns and with the first
+//           10 only (the fixed column left in place), interleaved rep by rep
 // Build: hipcc -O3 --offload-arch=gfx950 -o tools/store_probe tools/store_probe.hip
 #include <hip/hip_runtime.h>
 
@@ -361,7 +363,9 @@ __global__ void __launch_bounds__((NC + 1) * 64) wave_spec(uint32_t* adv, uint64
 //          line, the last tile leaves the quads of its last line to the boundary store, which
 //          so begins and ends on a line
 //   VAR 3: VAR 1 with the first tile's line owned as in VAR 2 (last half-round | final still split)
-template <int VAR>
+//   NC: the columns written, 11, or 10: the fixed column (the last) left in place, every other
+//       column at the address and line offset it has among 11
+template <int VAR, int NC = 11>
 __global__ void __launch_bounds__(256) fused_order_store(uint32_t* adv, uint64_t total_rows, uint32_t n,
                                                          unsigned* ctr) {
   constexpr uint32_t HRQ = 52, NHR = 24, IQ = 41, FQ = 16, RPI = 4 * (IQ + NHR * HRQ + FQ);
@@ -386,7 +390,7 @@ __global__ void __launch_bounds__(256) fused_order_store(uint32_t* adv, uint64_t
       const uint64_t row0 = (uint64_t)i * RPI + 4 * IQ + 4 * HRQ * h;
       const bool own_head = VAR >= 2 || h != 0, own_tail = VAR != 2 && h == NHR - 1;
 #pragma unroll
-      for (int c = 0; c < 11; c++) {
+      for (int c = 0; c < NC; c++) {
         const uint64_t w = (uint64_t)c * total_rows + row0;
         const uint32_t kc = own_head ? lq(w) : 0u, tc = own_tail ? 0u : lq(w + 4 * HRQ);
         put(w - 4 * kc, HRQ + kc - tc, i);
@@ -399,7 +403,7 @@ __global__ void __launch_bounds__(256) fused_order_store(uint32_t* adv, uint64_t
     if (b0 >= n_edge) break;
     for (uint32_t b = b0; b < b0 + 8 && b < n_edge; b++) {
 #pragma unroll
-      for (int c = 0; c < 11; c++) {
+      for (int c = 0; c < NC; c++) {
         const uint64_t w = (uint64_t)c * total_rows + (uint64_t)b * RPI;
         if (VAR == 0) {
           put(w, IQ, b);
@@ -451,6 +455,32 @@ int main(int argc, char** argv) {
     CHK(hipFree(ctr));
     CHK(hipMalloc(&ctr, 8));
     const int reps = argc > 3 ? atoi(argv[3]) : 7;
+    if (argc > 4 && atoi(argv[4]) == 10) {  // the product's order (whole lines) with and without the fixed column
+      float t[2][16];
+      for (int rep = 0; rep < reps && rep < 16; rep++)
+        for (int v = 0; v < 2; v++) {
+          CHK(hipMemset(ctr, 0, 8));
+          CHK(hipEventRecord(a));
+          if (v == 0) hipLaunchKernelGGL((fused_order_store<2, 11>), dim3(cus * 3), dim3(256), 0, 0, adv, total, n, ctr);
+          if (v == 1) hipLaunchKernelGGL((fused_order_store<2, 10>), dim3(cus * 3), dim3(256), 0, 0, adv, total, n, ctr);
+          CHK(hipEventRecord(b));
+          CHK(hipEventSynchronize(b));
+          CHK(hipEventElapsedTime(&t[v][rep], a, b));
+        }
+      for (int v = 0; v < 2; v++) {  // the first rep carries the warm-up: listed, not in min / max
+        float lo = 1e30f, hi = 0;
+        printf("{\"pattern\": \"fused_order_whole_lines\", \"cols\": %d, \"n\": %u, \"ms_all\": [", 11 - v, n);
+        for (int rep = 0; rep < reps && rep < 16; rep++) {
+          printf("%s%.3f", rep ? ", " : "", t[v][rep]);
+          if (rep && t[v][rep] < lo) lo = t[v][rep];
+          if (rep && t[v][rep] > hi) hi = t[v][rep];
+        }
+        printf("], \"ms_min\": %.3f, \"ms_max\": %.3f, \"TBs\": %.3f}\n", lo, hi,
+               (double)total * 4 * (11 - v) / lo / 1e9);
+      }
+      CHK(hipGetLastError());
+      return 0;
+    }
     const char* names[4] = {"fused_order_split", "fused_order_final_init_paired", "fused_order_whole_lines",
                             "fused_order_paired_head_owned"};
     float ms[4][16];

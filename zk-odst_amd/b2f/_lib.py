@@ -30,6 +30,7 @@ KERNEL_NAMES = ["record", "fill", "eval", "export", "fill_eval", "lookup", "perm
                 "perm_sigma", "ntt", "quotient"]  # B2F_KERNEL_*
 FP_CANONICAL, FP_MONTGOMERY, FP_BN254_CANONICAL, FP_BN254_MONTGOMERY = 0, 1, 2, 3  # B2F_FP_*
 NTT_FORWARD, NTT_INVERSE = 0, 1  # B2F_NTT_*
+FIXED_RESIDENT = 1  # B2F_FIXED_RESIDENT (b2f_fill_eval_dev_ex flags)
 
 OK, ERR_ARG, ERR_ROUNDS, ERR_ROWS, ERR_HIP, ERR_LAYOUT, ERR_INPUT, ERR_FIELD, ERR_CHECK = range(9)
 STATUS_NAMES = {OK: "OK", ERR_ARG: "B2F_ERR_ARG", ERR_ROUNDS: "B2F_ERR_ROUNDS",
@@ -97,6 +98,8 @@ SIGNATURES = [
     ("b2f_fill_dev", I32, [P, P, SIZE, P, U64, P, P, P, P]),
     ("b2f_eval_dev", I32, [P, P, P, P, SIZE, U64, P, P]),
     ("b2f_fill_eval_dev", I32, [P, P, SIZE, P, U64, P, P, P, P, P]),
+    ("b2f_fill_eval_dev_ex", I32, [P, P, SIZE, P, U64, P, P, P, P, ctypes.c_uint32, P]),
+    ("b2f_debug_fused_path", I32, [P, P]),
     ("b2f_debug_inject", I32, [P, U64, ctypes.c_uint32, ctypes.c_uint32]),
     ("b2f_debug_clock", I32, [P, P]),
     ("b2f_debug_eval_path", I32, [P, P]),

@@ -65,6 +65,7 @@ class Engine:
         self.lib = _lib.load(diag=diag, path=lib_path)
         self.diag = bool(diag or lib_path)
         self.device = int(device)
+        self.injecting = False  # debug_inject: the hook is on
         self.ctx = self.lib.b2f_create(self.device)
         if not self.ctx:
             raise _lib.B2FError(_lib.ERR_HIP, "b2f_create(%d) failed (no such HIP device?)" % device)
@@ -117,11 +118,20 @@ class Engine:
                                           int(total_rows), _vp(d_report), _vp(stream)))
 
     def fill_eval_dev(self, d_in, n, d_off, total_rows, d_adv, d_fixed, d_h_out, d_report,
-                      stream=0):
-        self._check(self.lib.b2f_fill_eval_dev(self.ctx, _vp(d_in), n, _vp(d_off),
-                                               int(total_rows), _vp(d_adv), _vp(d_fixed),
-                                               _vp(d_h_out) if d_h_out else None,
-                                               _vp(d_report), _vp(stream)))
+                      stream=0, flags=0):
+        """b2f_fill_eval_dev_ex; flags=_lib.FIXED_RESIDENT states that d_fixed already holds this
+        row map's fixed column (see include/b2f.h: the library checks its own record too). A
+        library built before that entry point (lib_path) gets the plain call, flags dropped."""
+        if not hasattr(self.lib, "b2f_fill_eval_dev_ex"):
+            self._check(self.lib.b2f_fill_eval_dev(self.ctx, _vp(d_in), n, _vp(d_off),
+                                                   int(total_rows), _vp(d_adv), _vp(d_fixed),
+                                                   _vp(d_h_out) if d_h_out else None,
+                                                   _vp(d_report), _vp(stream)))
+            return
+        self._check(self.lib.b2f_fill_eval_dev_ex(self.ctx, _vp(d_in), n, _vp(d_off),
+                                                  int(total_rows), _vp(d_adv), _vp(d_fixed),
+                                                  _vp(d_h_out) if d_h_out else None,
+                                                  _vp(d_report), int(flags), _vp(stream)))
 
     def fill_fixed_dev(self, d_off, n, total_rows, d_fixed, stream=0):
         """Keygen structure: the fixed column from the row map alone (b2f_fill_fixed_dev)."""
@@ -133,6 +143,7 @@ class Engine:
         it; row=None turns it off."""
         r = 2**64 - 1 if row is None else int(row)
         self._check(self.lib.b2f_debug_inject(self.ctx, r, int(col), int(mask) & 0xffffffff))
+        self.injecting = row is not None
 
     def chain_inputs_dev(self, d_h_prev, d_blocks, d_t, d_f, rounds, n, d_out, stream=0):
         self._check(self.lib.b2f_chain_inputs_dev(self.ctx, _vp(d_h_prev), _vp(d_blocks), _vp(d_t),
@@ -580,6 +591,13 @@ class Engine:
         self._check(self.lib.b2f_debug_eval_path(self.ctx, ctypes.byref(out)))
         return int(out.value)
 
+    def debug_fused_path(self):
+        """Kernel of the last fill_eval_dev call (host state, no synchronize): 0 the full one,
+        1 the advice-only one (FIXED_RESIDENT honoured)."""
+        out = ctypes.c_uint32(0)
+        self._check(self.lib.b2f_debug_fused_path(self.ctx, ctypes.byref(out)))
+        return int(out.value)
+
     def debug_field_op(self, op, a, b, field):
         """Diagnostics build only (b2f_debug_field_op): the field primitive `op` (a name of
         _lib.FIELD_OPS) on the device, one lane per element. a, b: uint64 [n, 4] host limbs, used as
@@ -671,23 +689,59 @@ class DeviceBatch:
         self.fixed = torch.empty(self.total_rows, dtype=torch.int32, device=dev)
         self.h_out = torch.empty((self.n, 8), dtype=torch.int64, device=dev)
         self.report = torch.empty(_lib.REPORT_BYTES // 8, dtype=torch.int64, device=dev)
+        self._fixed_seal = None
+
+    def _seal(self, eng):
+        """What must still hold at the next fill_evaluate for the fixed column to count as
+        resident: the engine's context and the version counters of `fixed` and `offsets` (torch
+        bumps a tensor's counter on every in-place write, through views too; reads leave it).
+        None -- never resident -- for a diagnostics or lib_path engine, under the inject hook, or
+        where the counters cannot be read."""
+        if eng.diag or eng.injecting:
+            return None
+        try:
+            return (eng.ctx, self.fixed.data_ptr(), self.fixed._version, self.offsets._version)
+        except Exception:
+            return None
+
+    def invalidate_fixed(self):
+        """Forget that `fixed` holds the keygen column: the next fill_evaluate writes it. For
+        writers torch's version counter does not see (.data, a foreign holder of data_ptr(),
+        DLPack)."""
+        self._fixed_seal = None
 
     def fill(self, eng, stream=None):
         s = stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
+        self._fixed_seal = None
         eng.fill_dev(self.inputs.data_ptr(), self.n, self.offsets.data_ptr(), self.total_rows,
                      self.advice.data_ptr(), self.fixed.data_ptr(), self.h_out.data_ptr(), s)
+        self._fixed_seal = self._seal(eng)
 
     def evaluate(self, eng, stream=None):
         s = stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
         eng.eval_dev(self.advice.data_ptr(), self.fixed.data_ptr(), self.offsets.data_ptr(),
                      self.n, self.total_rows, self.report.data_ptr(), s)
 
-    def fill_evaluate(self, eng, stream=None):
-        """Fused fill + eval (b2f_fill_eval_dev): trace, h' and report in one pass."""
+    def fill_evaluate(self, eng, stream=None, fixed_resident=None):
+        """Fused fill + eval (b2f_fill_eval_dev_ex): trace, h' and report in one pass.
+
+        The fixed column is a function of the row map alone (keygen output), so a repeat call
+        leaves it in place. fixed_resident=None decides that automatically: the call states
+        B2F_FIXED_RESIDENT only if this batch's last fill / fill_evaluate ran on this same
+        product engine with the inject hook off, and neither `fixed` nor `offsets` has been
+        written through torch since (their version counters are unchanged). Everything else --
+        a first call, another engine, a diagnostics or lib_path engine, the hook -- writes the
+        whole trace. fixed_resident=False always does. Writes torch cannot see (.data, a
+        foreign holder of data_ptr(), DLPack) are the caller's business: invalidate_fixed()."""
         s = stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
+        seal = self._seal(eng)
+        resident = fixed_resident is None and seal is not None and seal == self._fixed_seal
+        self._fixed_seal = None  # a call that raises leaves nothing resident
         eng.fill_eval_dev(self.inputs.data_ptr(), self.n, self.offsets.data_ptr(),
                           self.total_rows, self.advice.data_ptr(), self.fixed.data_ptr(),
-                          self.h_out.data_ptr(), self.report.data_ptr(), s)
+                          self.h_out.data_ptr(), self.report.data_ptr(), s,
+                          flags=_lib.FIXED_RESIDENT if resident else 0)
+        self._fixed_seal = seal
 
     def export_fp(self, eng, row_begin=0, nrows=None, form=_lib.FP_MONTGOMERY, out=None,
                   stream=None):

@@ -281,7 +281,15 @@ __device__ __forceinline__ void producer_words(uint64_t* prod, const Ops& P, uin
 #define B2F_FUSED_HR_PER_CU 3  // half-round launch: workgroups per CU (at most what fits)
 #endif
 enum { FZ_LOOKUP = 1, FZ_STORE = 2, FZ_INJECT = 4, FZ_GATES = 8, FZ_COPIES = 16, FZ_FULL = 27,
+       FZ_NOFIX = 32,     // the fixed column is resident (B2F_FIXED_RESIDENT): no store to it
        FZ_CLOCK = 128 };  // per-phase s_memtime totals per wave slot (diagnostics, b2f_debug_clock)
+// The columns a tile stores: the fixed column (the last staged one) is a function of the row map
+// alone, keygen output. Under FZ_NOFIX it is still formed, staged and checked in LDS -- the fast
+// checks read it there, and the tile's transients live in its staging -- but not written: a
+// repeat call on the same row map and buffers leaves the 4 of its 44 bytes per row in place.
+static_assert(FZ_NOFIX == FUSED_MODE_NOFIX, "b2f_launch.h names the bit for the C ABI file");
+template <int MODE>
+constexpr int store_cols() { return (MODE & FZ_NOFIX) ? NSTAGE - 1 : NSTAGE; }
 
 // Stores of a tile: raw buffer stores through a per-tile, per-column buffer resource whose
 // range is the tile's quads, so every lane of the wave issues the same store instructions and
@@ -1412,7 +1420,8 @@ fused_hr_kernel(const b2f_input* __restrict__ in, uint32_t n, const uint64_t* __
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's staging is complete
       __builtin_amdgcn_wave_barrier();
       // ---- 5. stores, then the wait for the next tile's word: vmcnt counts loads and stores
-      // in issue order, so placed after this tile's 11 stores it is vmcnt(11) -- the load and
+      // in issue order, so placed after this tile's 11 stores (10 under FZ_NOFIX) it is vmcnt(11)
+      // (vmcnt(10)) -- the load and
       // the PREVIOUS tile's stores, issued a tile ago -- never a wait for these stores
       tick(3);
       // Line ownership: a 208-row tile is 832 bytes per column, so tile boundaries fall inside
@@ -1440,7 +1449,7 @@ fused_hr_kernel(const b2f_input* __restrict__ in, uint32_t n, const uint64_t* __
         if (MODE & FZ_STORE) tile_store(base - 4 * kc, HR_Q + kc - tc, lane, v);
       };
 #pragma unroll
-      for (int col = 0; col < NSTAGE; col++) store_col(col);
+      for (int col = 0; col < store_cols<MODE>(); col++) store_col(col);
       // the lookup and fixed checks read the lane's quad (lane_quad: its K program)
       const uint32_t ls = lane_quad(lane);
       const uint4 cq0 = *reinterpret_cast<const uint4*>(S + A0 * HSTR + 4 * ls);
@@ -2064,7 +2073,7 @@ __device__ __forceinline__ void edge_walk(uint32_t* S, uint32_t lane, uint64_t t
             return v;
           };
 #pragma unroll
-          for (int col = 0; col < NSTAGE; col++) {
+          for (int col = 0; col < store_cols<MODE>(); col++) {
             const uint4 sv = *reinterpret_cast<const uint4*>(S + col * STR_E + 4 * l);
             const uint4 tq = tail_cells(col);
             const uint4 cv = tlane ? tq : sv;
@@ -2118,7 +2127,7 @@ __device__ __forceinline__ void edge_walk(uint32_t* S, uint32_t lane, uint64_t t
         }
         if (MODE & FZ_STORE) {
 #pragma unroll
-          for (int cc = 0; cc < 11; cc++)
+          for (int cc = 0; cc < store_cols<MODE>(); cc++)
             tile_store((cc < 10 ? adv + (uint64_t)cc * total_rows : fixed) + row0, nq, lane,
                        cc < 10 ? make_uint4(Q.c[cc][0], Q.c[cc][1], Q.c[cc][2], Q.c[cc][3])
                                : make_uint4(Q.fx[0], Q.fx[1], Q.fx[2], Q.fx[3]));
@@ -2724,9 +2733,10 @@ hipError_t launch_fill_eval(const b2f_input* d_in, uint32_t n, const uint64_t* d
   inj.col = inj_col;
   inj.mask = inj_mask;
 #ifndef B2F_DIAG
-  mode = FZ_FULL;  // the product library launches the full kernel only
+  // the product library launches the full kernel only, or its advice-only instantiation
+  mode = FZ_FULL | (mode & FZ_NOFIX);
 #endif
-  if (inj_row != ~0ull) mode |= FZ_INJECT;
+  if (inj_row != ~0ull) mode = (mode & ~FZ_NOFIX) | FZ_INJECT;  // the hook's cell may be a fixed one
   // persistent grid: the workgroups that are resident at once (VGPRs and LDS bound them)
   static int per_cu[2] = {0, 0};
   if (!per_cu[0]) {
@@ -2773,13 +2783,15 @@ hipError_t launch_fill_eval(const b2f_input* d_in, uint32_t n, const uint64_t* d
       hipLaunchKernelGGL(fused_edge_kernel<M>, dim3(grid_e), dim3(FW * WAVES), 0, s, d_in, n, d_off, \
                          total_rows, rec, d_adv, d_fixed, redo, d_rep, d_status, inj, defer,       \
                          DEFER_CAP, clk);                                                          \
-    hipLaunchKernelGGL(edge_redo_kernel<M>, dim3(cu_count), dim3(FW * WAVES), 0, s, d_in, d_off,   \
+    hipLaunchKernelGGL(edge_redo_kernel<(M) & ~FZ_NOFIX>, dim3(cu_count), dim3(FW * WAVES), 0, s, d_in, d_off,   \
                        total_rows, rec, d_adv, d_fixed, redo, d_rep, d_status, inj, defer,         \
                        DEFER_CAP);                                                                 \
     break;
 #ifdef B2F_DIAG
     B2F_FUSED(0) B2F_FUSED(2) B2F_FUSED(3) B2F_FUSED(10) B2F_FUSED(18) B2F_FUSED(8) B2F_FUSED(16)
     B2F_FUSED(FZ_FULL | FZ_CLOCK) B2F_FUSED(2 | FZ_CLOCK) B2F_FUSED(0 | FZ_CLOCK)
+#else
+    B2F_FUSED(FZ_FULL | FZ_NOFIX)  // b2f_fill_eval_dev_ex with B2F_FIXED_RESIDENT honoured
 #endif
     B2F_FUSED(FZ_FULL | FZ_INJECT)
     default: B2F_FUSED(FZ_FULL)

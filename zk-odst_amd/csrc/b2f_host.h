@@ -42,6 +42,13 @@ struct b2f_ctx {
   const uint32_t* d_eval_gate;  // the last eval's fast-pass word (0: the fast pass found the trace clean)
   uint64_t inj_row;    // b2f_debug_inject (UINT64_MAX: off)
   uint32_t inj_col, inj_mask;
+  // the last full write of a fixed column by the fused call (b2f_fill_eval_dev[_ex]), hook off:
+  // B2F_FIXED_RESIDENT is honoured only for a call with these arguments (fx_fixed null: none)
+  const uint32_t* fx_fixed;
+  const uint64_t* fx_offsets;
+  size_t fx_n;
+  uint64_t fx_rows;
+  uint32_t fused_path;  // b2f_debug_fused_path: 1 the last fused call ran advice-only, 0 full
   void* d_lk;          // lookup-column scratch (b2f_lookup.hip carve)
   size_t lk_cap;
   void* d_fz;          // fused-path scratch: tile descriptors + deferred rows (b2f_fused.hip)

@@ -117,6 +117,9 @@ uint64_t fused_instance_tiles(uint64_t total_rows, uint64_t n);
 hipError_t launch_eval_fast(const uint32_t* d_adv, const uint32_t* d_fixed, const uint64_t* d_off, uint32_t n,
                             uint64_t total_rows, void* scratch, uint64_t tiles, const int* d_status,
                             int cu_count, hipStream_t s, const uint32_t** gate, int mode);
+// `mode` bit of launch_fill_eval (FZ_NOFIX): the launch leaves the fixed column unwritten. The
+// product library honours it (and no other bit); a call under the inject hook runs full.
+constexpr int FUSED_MODE_NOFIX = 32;
 hipError_t launch_fill_eval(const b2f_input* d_in, uint32_t n, const uint64_t* d_off,
                             uint64_t total_rows, const uint64_t* rec, uint32_t* d_adv,
                             uint32_t* d_fixed, void* scratch, uint64_t tiles,
