@@ -620,6 +620,42 @@ B2F_API int b2f_msm_dev(b2f_ctx* ctx, const uint64_t* d_scalars, uint64_t rows, 
 B2F_API int b2f_msm_plan(uint64_t len, uint32_t n_cols, uint32_t form, uint32_t* window_bits,
                          uint32_t* windows, uint32_t* group, uint64_t* scratch_bytes);
 
+/* The rounds of the inner product argument's opening (halo2's pasta backend:
+ * poly/commitment/prover.rs::create_proof's loop) over three device vectors of length len = 2^j:
+ * the coefficients p and the powers b, scalars d[i * 4 + limb] in `form` (any B2F_FP_*, reduced), and
+ * the generators G, points in b2f_msm_dev's layout (64 bytes, base-field Montgomery coordinates, the
+ * identity all zero, not checked to be on the curve). Forms 0/1 are Vesta, forms 2/3 BN254 G1. With
+ * half = len / 2, one round is
+ *   L = <p[half..], G[..half]>         R = <p[..half], G[half..]>          (b2f_ipa_round_dev)
+ *   value_l = <p[half..], b[..half]>   value_r = <p[..half], b[half..]>
+ *   caller: L += [value_l z] U + [l_rand] W, the same for R; writes both; squeezes u
+ *   p[i] += p[half+i] u^-1   b[i] += b[half+i] u   G[i] = affine(G[i] + [u] G[half+i])   (b2f_ipa_fold_dev)
+ * and after log2(len) rounds c = p[0]. The transcript, the blinding scalars, the s_poly masking and
+ * the U / W terms stay with the caller; every challenge is a host argument (canonical limbs).
+ * All three calls are asynchronous on `stream`, take 16-byte aligned pointers, use the context's
+ * scratch and are one B2F_KERNEL_QUOTIENT region each. Errors, nothing launched and the next good
+ * call works: B2F_ERR_ARG for a null or misaligned pointer, form > 3, a len that is not a power of
+ * two in [2, 2^28] (powers: len == 0 or > 2^28), h_x >= p, h_u >= p or h_u == 0, d_lr or d_values
+ * overlapping an input or each other, the three vectors overlapping each other; B2F_ERR_HIP for
+ * runtime failures, scratch growth included; B2F_ERR_CHECK at b2f_sync if an affine conversion's
+ * inversion fails on a non-identity point (a library defect, as for b2f_msm_dev). */
+/* d_b[i] = x^i, i < len, in `form` */
+B2F_API int b2f_ipa_powers_dev(b2f_ctx* ctx, const uint64_t h_x[4], uint64_t len, uint32_t form,
+                               uint64_t* d_b, void* stream);
+/* d_lr[0..7] = L, d_lr[8..15] = R (affine, the identity as zeros: bit-exact); d_values[0..3] =
+ * value_l, d_values[4..7] = value_r (fully reduced, in `form`). Reads all len elements of the three
+ * vectors and writes nothing else. A round of len <= b2f_ipa_direct_max_len() is one launch; a
+ * longer one is a single two-column Pippenger pass plus a tiled inner product. */
+B2F_API int b2f_ipa_round_dev(b2f_ctx* ctx, const uint64_t* d_p, const uint64_t* d_b,
+                              const uint64_t* d_g, uint64_t len, uint32_t form, uint64_t* d_lr,
+                              uint64_t* d_values, void* stream);
+/* The three collapses in place on i < half; elements at i >= half are read and never written. u^-1 is
+ * formed on the host. */
+B2F_API int b2f_ipa_fold_dev(b2f_ctx* ctx, uint64_t* d_p, uint64_t* d_b, uint64_t* d_g, uint64_t len,
+                             const uint64_t h_u[4], uint32_t form, void* stream);
+/* host only: the longest round b2f_ipa_round_dev runs as one direct launch (a power of two) */
+B2F_API uint64_t b2f_ipa_direct_max_len(void);
+
 /* The advice queries of the chip: the (halo2 advice column, rotation) pairs the sixteen gates read
  * (the list at b2f_quotient_gates_dev), as a set, sorted by column then rotation; writes
  * min(count, cap) pairs (column, rotation) and returns count. These are the evaluations of advice
@@ -644,7 +680,8 @@ B2F_API uint64_t b2f_gate_queries(uint32_t* pairs, uint64_t cap);
 #define B2F_KERNEL_PERM_SIGMA 7 /* permutation keygen: the sigma columns (b2f_permutation_sigma_dev) */
 #define B2F_KERNEL_NTT 8    /* NTT of prover columns (table build and all passes of one call) */
 #define B2F_KERNEL_QUOTIENT 9 /* quotient terms, the vanishing divide, the Lagrange selectors and the
-                                 evaluation / opening calls; the commitments (b2f_msm_dev) */
+                                 evaluation / opening calls; the commitments (b2f_msm_dev);
+                                 the IPA rounds (b2f_ipa_*_dev) */
 #define B2F_NUM_KERNELS 10
 /* total_ms and count must each hold b2f_num_kernels() entries (= B2F_NUM_KERNELS of the
  * header the library was built with; it grew from 7 to 8 with B2F_KERNEL_PERM_SIGMA, to 9

@@ -137,6 +137,10 @@ SIGNATURES = [
     ("b2f_kate_divide_dev", I32, [P, P, U64, U64, ctypes.c_uint32, P, P, ctypes.c_uint32, P, U64, P]),
     ("b2f_msm_dev", I32, [P, P, U64, U64, ctypes.c_uint32, P, U64, ctypes.c_uint32, P, P]),
     ("b2f_msm_plan", I32, [U64, ctypes.c_uint32, ctypes.c_uint32, P, P, P, P]),
+    ("b2f_ipa_powers_dev", I32, [P, P, U64, ctypes.c_uint32, P, P]),
+    ("b2f_ipa_round_dev", I32, [P, P, P, P, U64, ctypes.c_uint32, P, P, P]),
+    ("b2f_ipa_fold_dev", I32, [P, P, P, P, U64, P, ctypes.c_uint32, P]),
+    ("b2f_ipa_direct_max_len", U64, []),
     ("b2f_gate_queries", U64, [P, U64]),
     ("b2f_sync", I32, [P, P]),
     ("b2f_fill", I32, [P, P, SIZE, P, P, P]),
@@ -229,6 +233,12 @@ def msm_plan(len_, n_cols, form=FP_MONTGOMERY, diag=False):
         raise B2FError(rc, "no msm plan for len = %d, n_cols = %d, form = %d" % (len_, n_cols, form))
     return {"window_bits": int(c.value), "windows": int(w.value), "group": int(g.value),
             "scratch_bytes": int(sb.value)}
+
+
+def ipa_direct_max_len(diag=False):
+    """Host only (b2f_ipa_direct_max_len): the longest round b2f_ipa_round_dev runs as one direct
+    launch. diag=True asks the diagnostics library, which honours B2F_DIAG_IPA_DIRECT=<len>."""
+    return int(load(diag=diag).b2f_ipa_direct_max_len())
 
 
 def check(ctx, rc, lib=None):

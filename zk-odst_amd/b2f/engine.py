@@ -556,6 +556,71 @@ class Engine:
                      out.data_ptr(), s)
         return out
 
+    # ---------------------------------------------------------------- IPA opening rounds
+    def ipa_powers_dev(self, x, len_, form, d_b, stream=0):
+        """b2f_ipa_powers_dev: d_b[i] = x^i for i < len, in `form`; x a Python int (canonical)."""
+        self._check(self.lib.b2f_ipa_powers_dev(self.ctx, _np_ptr(self._elems([x])), int(len_), int(form),
+                                                _vp(d_b), _vp(stream)))
+
+    def ipa_round_dev(self, d_p, d_b, d_g, len_, form, d_lr, d_values, stream=0):
+        """b2f_ipa_round_dev: the round's cross terms (L, R) and inner products (value_l, value_r)."""
+        self._check(self.lib.b2f_ipa_round_dev(self.ctx, _vp(d_p), _vp(d_b), _vp(d_g), int(len_), int(form),
+                                               _vp(d_lr), _vp(d_values), _vp(stream)))
+
+    def ipa_fold_dev(self, d_p, d_b, d_g, len_, u, form, stream=0):
+        """b2f_ipa_fold_dev: the three collapses in place; u a Python int (canonical, non-zero)."""
+        self._check(self.lib.b2f_ipa_fold_dev(self.ctx, _vp(d_p), _vp(d_b), _vp(d_g), int(len_),
+                                              _np_ptr(self._elems([u])), int(form), _vp(stream)))
+
+    @staticmethod
+    def _ipa_vectors(name, p, b, g, n):
+        import torch
+
+        for what, t, w in (("p", p, 4), ("b", b, 4), ("g", g, 8)):
+            if t.dim() != 2 or t.shape[1] != w or t.dtype != torch.int64 or not t.is_contiguous():
+                raise _lib.B2FError(_lib.ERR_ARG, "%s: %s must be contiguous int64 [rows, %d]" % (name, what, w))
+            if int(t.shape[0]) < n:
+                raise _lib.B2FError(_lib.ERR_ROWS, "%s: %s holds fewer than len = %d rows" % (name, what, n))
+
+    def ipa_powers(self, x, len, form=_lib.FP_MONTGOMERY, out=None, stream=None):
+        """b = (1, x, x^2, ..) (b2f_ipa_powers_dev): int64 [len, 4] in `form`; x a Python int."""
+        import torch
+
+        n = int(len)
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.int64, device="cuda:%d" % self.device)
+        if out.dim() != 2 or out.shape[1] != 4 or out.dtype != torch.int64 or not out.is_contiguous() \
+                or int(out.shape[0]) < n:
+            raise _lib.B2FError(_lib.ERR_ARG, "ipa_powers: out must be contiguous int64 [rows >= len, 4]")
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.ipa_powers_dev(x, n, form, out.data_ptr(), s)
+        return out
+
+    def ipa_round(self, p, b, g, len=None, form=_lib.FP_MONTGOMERY, stream=None):
+        """One round's cross terms and inner products (b2f_ipa_round_dev). p, b: int64 [rows, 4]
+        scalars in `form`; g: int64 [rows, 8] affine points (curve.pack_points); the first `len`
+        rows (default: all of p) are the round's vectors. Returns (int64 [2, 8] = (L, R) affine,
+        the identity all zeros; int64 [2, 4] = (value_l, value_r) in `form`)."""
+        import torch
+
+        n = int(p.shape[0]) if len is None else int(len)
+        self._ipa_vectors("ipa_round", p, b, g, n)
+        lr = torch.empty((2, 8), dtype=torch.int64, device=p.device)
+        values = torch.empty((2, 4), dtype=torch.int64, device=p.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.ipa_round_dev(p.data_ptr(), b.data_ptr(), g.data_ptr(), n, form, lr.data_ptr(), values.data_ptr(), s)
+        return lr, values
+
+    def ipa_fold(self, p, b, g, u, len=None, form=_lib.FP_MONTGOMERY, stream=None):
+        """The round's collapses in place on rows below len / 2 (b2f_ipa_fold_dev); u a Python int,
+        the round's challenge. Rows from len / 2 on are left as they are."""
+        import torch
+
+        n = int(p.shape[0]) if len is None else int(len)
+        self._ipa_vectors("ipa_fold", p, b, g, n)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.ipa_fold_dev(p.data_ptr(), b.data_ptr(), g.data_ptr(), n, u, form, s)
+
     def debug_curve_op(self, op, a, b, curve, za=None, zb=None):
         """Diagnostics build only (b2f_debug_curve_op): the base-field primitive or point operation
         `op` (a name of _lib.CURVE_OPS) on the device, one lane per element. Field ops: a, b uint64

@@ -794,6 +794,166 @@ B2F_API int b2f_msm_dev(b2f_ctx* ctx, const uint64_t* d_scalars, uint64_t rows, 
   return B2F_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// Host field helpers of the IPA fold: x R mod p of a canonical x (256 doublings mod p: p < 2^255,
+// so 2x never leaves four limbs) and x^-1 mod p by the divsteps of b2f_safegcd.h.
+void host_to_mont(uint32_t form, const uint64_t* x, uint64_t* out) {
+  field::with_field(form, [&](auto f) {
+    using F = decltype(f);
+    uint64_t p[4], v[4];
+    for (int i = 0; i < 4; i++) {
+      p[i] = ((uint64_t)F::P[2 * i + 1] << 32) | F::P[2 * i];
+      v[i] = x[i];
+    }
+    for (int step = 0; step < 256; step++) {
+      for (int i = 3; i > 0; i--) v[i] = (v[i] << 1) | (v[i - 1] >> 63);
+      v[0] <<= 1;
+      bool ge = true;
+      for (int i = 3; i >= 0; i--)
+        if (v[i] != p[i]) {
+          ge = v[i] > p[i];
+          break;
+        }
+      if (ge) {
+        uint64_t br = 0;
+        for (int i = 0; i < 4; i++) {
+          const unsigned __int128 d = (unsigned __int128)v[i] - p[i] - br;
+          v[i] = (uint64_t)d;
+          br = (uint64_t)(d >> 64) & 1;
+        }
+      }
+    }
+    for (int i = 0; i < 4; i++) out[i] = v[i];
+    return 0;
+  });
+}
+bool host_inverse(uint32_t form, const uint64_t* x, uint64_t* out) {
+  return field::with_field(form, [&](auto f) {
+    using F = decltype(f);
+    uint32_t xw[8], pw[8], ow[8];
+    for (int i = 0; i < 8; i++) {
+      xw[i] = (uint32_t)(x[i >> 1] >> (32 * (i & 1)));
+      pw[i] = F::P[i];
+    }
+    const bool ok = sgcd::inverse(xw, pw, ow);
+    for (int i = 0; i < 4; i++) out[i] = ((uint64_t)ow[2 * i + 1] << 32) | ow[2 * i];
+    return ok;
+  });
+}
+
+// The longest round the direct kernel takes: the plan constant, or under the diagnostics library
+// what B2F_DIAG_IPA_DIRECT forces. false: the forced value is malformed.
+bool ipa_direct_for(uint64_t* max_len) {
+  *max_len = ipa_direct_max_len();
+#ifdef B2F_DIAG
+  uint64_t forced = 0;
+  const int have = diag_ipa_direct(&forced);
+  if (have < 0) return false;
+  if (have) *max_len = forced;
+#endif
+  return true;
+}
+
+// what the round and fold calls check alike
+int ipa_check_vectors(b2f_ctx* ctx, const char* what, const uint64_t* d_p, const uint64_t* d_b, const uint64_t* d_g,
+                      uint64_t len, uint32_t form) {
+  if (!d_p || !d_b || !d_g) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (((uintptr_t)d_p | (uintptr_t)d_b | (uintptr_t)d_g) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "%s: buffers must be 16-byte aligned", what);
+  if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "%s: unknown form %u", what, form);
+  if (len < 2 || len > (1ull << 28) || (len & (len - 1)))
+    return set_err(ctx, B2F_ERR_ARG, "%s: len %llu is not a power of two in [2, 2^28]", what, (unsigned long long)len);
+  if (ranges_overlap(d_p, 32 * len, d_b, 32 * len) || ranges_overlap(d_p, 32 * len, d_g, 64 * len) ||
+      ranges_overlap(d_b, 32 * len, d_g, 64 * len))
+    return set_err(ctx, B2F_ERR_ARG, "%s: the three vectors overlap", what);
+  return B2F_OK;
+}
+}  // namespace
+
+extern "C" {
+
+B2F_API uint64_t b2f_ipa_direct_max_len(void) {
+  uint64_t m = 0;
+  if (!ipa_direct_for(&m)) return ipa_direct_max_len();
+  return m;
+}
+
+B2F_API int b2f_ipa_powers_dev(b2f_ctx* ctx, const uint64_t h_x[4], uint64_t len, uint32_t form, uint64_t* d_b,
+                               void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "ipa powers";
+  if (!h_x || !d_b) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if ((uintptr_t)d_b & 15) return set_err(ctx, B2F_ERR_ARG, "%s: d_b must be 16-byte aligned", what);
+  if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "%s: unknown form %u", what, form);
+  if (len == 0 || len > (1ull << 28))
+    return set_err(ctx, B2F_ERR_ARG, "%s: len %llu not in [1, 2^28]", what, (unsigned long long)len);
+  if (!fe_canonical(form, h_x)) return set_err(ctx, B2F_ERR_ARG, "%s: x is >= p", what);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_ipa_powers(h_x, len, form, d_b, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API int b2f_ipa_round_dev(b2f_ctx* ctx, const uint64_t* d_p, const uint64_t* d_b, const uint64_t* d_g,
+                              uint64_t len, uint32_t form, uint64_t* d_lr, uint64_t* d_values, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "ipa round";
+  if (!d_lr || !d_values) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (((uintptr_t)d_lr | (uintptr_t)d_values) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "%s: buffers must be 16-byte aligned", what);
+  if (int rc = ipa_check_vectors(ctx, what, d_p, d_b, d_g, len, form)) return rc;
+  const struct {
+    const void* at;
+    uint64_t bytes;
+  } in[3] = {{d_p, 32 * len}, {d_b, 32 * len}, {d_g, 64 * len}};
+  for (const auto& v : in)
+    if (ranges_overlap(d_lr, 128, v.at, v.bytes) || ranges_overlap(d_values, 64, v.at, v.bytes))
+      return set_err(ctx, B2F_ERR_ARG, "%s: an output overlaps an input", what);
+  if (ranges_overlap(d_lr, 128, d_values, 64)) return set_err(ctx, B2F_ERR_ARG, "%s: the outputs overlap", what);
+  uint64_t direct_max = 0;
+  if (!ipa_direct_for(&direct_max)) return set_err(ctx, B2F_ERR_ARG, "%s: the forced switch-over is malformed", what);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (len <= direct_max) {
+    int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+    HIPCHK(ctx, launch_ipa_round_direct(d_p, d_b, d_g, len, form, d_lr, d_values, ctx->d_status + 2, s));
+    timed_end(ctx, tk, s);
+    return B2F_OK;
+  }
+  MsmPlan plan;
+  if (!msm_plan_of(len / 2, 2, 0, 0, &plan)) return set_err(ctx, B2F_ERR_ARG, "%s: no plan", what);
+  if (int rc = grow_device(ctx, &ctx->d_msm, &ctx->msm_cap, plan.scratch_bytes, 1, s)) return rc;
+  if (int rc = grow_device(ctx, &ctx->d_ipa, &ctx->ipa_cap, ipa_scratch_bytes(len), 1, s)) return rc;
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_ipa_round_long(plan, d_p, d_b, d_g, len, form, d_lr, d_values, ctx->d_msm, ctx->d_ipa,
+                                    ctx->d_status + 2, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API int b2f_ipa_fold_dev(b2f_ctx* ctx, uint64_t* d_p, uint64_t* d_b, uint64_t* d_g, uint64_t len,
+                             const uint64_t h_u[4], uint32_t form, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "ipa fold";
+  if (!h_u) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (int rc = ipa_check_vectors(ctx, what, d_p, d_b, d_g, len, form)) return rc;
+  if (!fe_canonical(form, h_u) || fe_is_zero(h_u)) return set_err(ctx, B2F_ERR_ARG, "%s: u is zero or >= p", what);
+  uint64_t uinv[4], u_mont[4], uinv_mont[4];
+  if (!host_inverse(form, h_u, uinv)) return set_err(ctx, B2F_ERR_CHECK, "%s: the host inversion of u failed", what);
+  host_to_mont(form, h_u, u_mont);
+  host_to_mont(form, uinv, uinv_mont);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_ipa_fold(d_p, d_b, d_g, len, h_u, u_mont, uinv_mont, form, ctx->d_status + 2, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
 B2F_API uint64_t b2f_gate_queries(uint32_t* pairs, uint64_t cap) { return gate_queries(pairs, cap); }
 
 B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_rows,

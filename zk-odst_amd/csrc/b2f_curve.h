@@ -164,6 +164,31 @@ __device__ __forceinline__ Xyzz add(const Xyzz& a, const Xyzz& b) {
   return o;
 }
 
+// k * p for a canonical scalar k (any 256-bit integer) and an affine p, left-to-right double and
+// add with mixed additions: the full-width sibling of b2f_msm.hip's 16-bit small_mul. About
+// 9 products per bit below the top one and 10 per set bit. The scalar is shifted left a bit a step
+// and its top bit tested, so no word of it is indexed by a variable; leading zero bits cost the
+// shift alone. With a scalar the whole wave shares (a kernel argument: b2f_ipa.hip's collapse) the
+// branch is uniform.
+template <class F>
+__device__ Xyzz scalar_mul(const Affine& p, Fe k) {
+  Xyzz r = xyzz_identity();
+  if (is_identity(p)) return r;
+  bool started = false;
+#pragma unroll 1
+  for (int b = 0; b < 256; b++) {
+    const bool bit = k.w[7] >> 31;
+#pragma unroll
+    for (int i = 7; i > 0; i--) k.w[i] = (k.w[i] << 1) | (k.w[i - 1] >> 31);
+    k.w[0] <<= 1;
+    if (!started && !bit) continue;
+    if (started) r = dbl<F>(r);
+    if (bit) r = madd<F>(r, p);
+    started = true;
+  }
+  return r;
+}
+
 // The affine form of p (the identity: all zero): one inversion (of ZZZ; 1 / ZZ = (ZZ / ZZZ)^2
 // since ZZ^3 = ZZZ^2) and five products. `ok` is inv_safegcd's.
 template <class F>

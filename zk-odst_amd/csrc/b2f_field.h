@@ -397,6 +397,13 @@ __device__ __forceinline__ Fe to_mont(const Fe& a) {
   return mul<F>(a, fe_const<F>(F::R2));
 }
 
+// z^t in Montgomery form for a canonical z: one entry of a power table, one lane each (the opening
+// step's point tables in b2f_open.hip, the IPA's b vector in b2f_ipa.hip)
+template <class F>
+__device__ __forceinline__ Fe pow_entry(const Fe& z_canonical, uint32_t t) {
+  return fe_pow<F>(to_mont<F>(z_canonical), t);
+}
+
 // canonical value of a Montgomery-form element (PrimeField::to_repr as integer words)
 template <class F>
 __device__ __forceinline__ Fe to_canonical(const Fe& a) {

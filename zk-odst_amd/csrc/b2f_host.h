@@ -89,6 +89,8 @@ struct b2f_ctx {
   size_t op_cap;
   void* d_msm;  // commitment scratch (b2f_msm.hip: msm_plan_of carves it)
   size_t msm_cap;
+  void* d_ipa;  // IPA round scratch beyond the commitments' (b2f_ipa.hip: ipa_scratch_bytes)
+  size_t ipa_cap;
 };
 
 namespace b2f {

@@ -1169,6 +1169,7 @@ B2F_API void b2f_destroy(b2f_ctx* ctx) {
   (void)hipFree(ctx->d_op_blob);
   (void)hipFree(ctx->d_op);
   (void)hipFree(ctx->d_msm);
+  (void)hipFree(ctx->d_ipa);
   if (ctx->op_ev_live) (void)hipEventSynchronize(ctx->op_ev);
   if (ctx->op_ev) (void)hipEventDestroy(ctx->op_ev);
   (void)hipHostFree(ctx->h_op);

@@ -97,11 +97,36 @@ struct MsmPlan {
 };
 uint32_t msm_default_window(uint64_t len);
 bool msm_plan_of(uint64_t len, uint32_t n_cols, uint32_t force_c, uint32_t force_g, MsmPlan* plan);
+// base_offsets (optional, calls of at most MSM_OFFSET_COLS columns): column c reads base
+// row + v[c] where the others read base row; row + v[c] < 2^28 is the caller's to keep.
+constexpr uint32_t MSM_OFFSET_COLS = 4;
+struct MsmBaseOffsets {
+  uint32_t v[MSM_OFFSET_COLS];
+};
 hipError_t launch_msm(const MsmPlan& plan, const uint64_t* d_scalars, uint64_t rows, uint64_t len, uint32_t n_cols,
                       const uint64_t* d_bases, uint32_t form, uint64_t* d_out, void* scratch, int* sticky,
-                      hipStream_t s);
+                      hipStream_t s, const MsmBaseOffsets* base_offsets = nullptr);
 #ifdef B2F_DIAG
 int diag_msm_plan(uint32_t* c, uint32_t* g);
+#endif
+
+// b2f_ipa.hip: the IPA opening rounds. A round of len <= ipa_direct_max_len() is one direct launch;
+// a longer one is a two-column launch_msm with base offsets (its plan: msm_plan_of(len / 2, 2, ..),
+// its scratch the commitments') plus the inner products, which need ipa_scratch_bytes(len). u, u_mont,
+// uinv_mont: the challenge as canonical limbs, and it and its inverse in Montgomery form (host).
+uint64_t ipa_direct_max_len();
+size_t ipa_scratch_bytes(uint64_t len);
+hipError_t launch_ipa_powers(const uint64_t* x, uint64_t len, uint32_t form, uint64_t* d_b, hipStream_t s);
+hipError_t launch_ipa_round_direct(const uint64_t* d_p, const uint64_t* d_b, const uint64_t* d_g, uint64_t len,
+                                   uint32_t form, uint64_t* d_lr, uint64_t* d_values, int* sticky, hipStream_t s);
+hipError_t launch_ipa_round_long(const MsmPlan& plan, const uint64_t* d_p, const uint64_t* d_b, const uint64_t* d_g,
+                                 uint64_t len, uint32_t form, uint64_t* d_lr, uint64_t* d_values, void* msm_scratch,
+                                 void* ipa_scratch, int* sticky, hipStream_t s);
+hipError_t launch_ipa_fold(uint64_t* d_p, uint64_t* d_b, uint64_t* d_g, uint64_t len, const uint64_t* u,
+                           const uint64_t* u_mont, const uint64_t* uinv_mont, uint32_t form, int* sticky,
+                           hipStream_t s);
+#ifdef B2F_DIAG
+int diag_ipa_direct(uint64_t* len);
 #endif
 
 // b2f_export.hip

@@ -9,7 +9,9 @@
 //      d in [-2^(c-1), 2^(c-1)] (a digit above 2^(c-1) borrows 2^c from the next window). A digit
 //      is the pair (key, value): key = (column, window, |d| - 1), value = the base's index with the
 //      sign in bit 31. Zero digits get the key one past the last bucket and the EMPTY bit: they
-//      sort to the end and cost no point addition. windows * c >= 256 and every scalar is below
+//      sort to the end and cost no point addition. A call may give each of its (at most four)
+//      columns an offset added to the base's index: column c then runs against bases[off_c ..]
+//      (the IPA round's two cross terms, b2f_ipa.hip). windows * c >= 256 and every scalar is below
 //      2^255, so the top window never carries out.
 //   2. rocprim::radix_sort_pairs groups the digits by key.
 //   3. bucket sums, as a reduction by key in levels (reduce_kernel): a level cuts its sorted
@@ -144,7 +146,8 @@ template <class C, bool MONT>
 __global__ __launch_bounds__(256) void recode_kernel(const uint64_t* __restrict__ scalars, uint64_t rows,
                                                      uint64_t r0, uint32_t rc, uint32_t col0, uint32_t gc,
                                                      uint32_t c, uint32_t windows, uint32_t buckets,
-                                                     uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+                                                     const MsmBaseOffsets boff, uint32_t* __restrict__ keys,
+                                                     uint32_t* __restrict__ vals) {
   using FS = typename C::Scalar;
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (uint64_t)gc * rc) return;
@@ -152,6 +155,9 @@ __global__ __launch_bounds__(256) void recode_kernel(const uint64_t* __restrict_
   Fe v = load(scalars + ((uint64_t)(col0 + cl) * rows + r0 + r) * 4);
   if (MONT) v = to_canonical<FS>(v);
   const uint32_t half = 1u << (c - 1), sentinel = (gc * windows * buckets) | EMPTY;
+  // the column's base offset (all zero unless the call gave any): selected, not indexed
+  const uint32_t ci = col0 + cl;
+  const uint32_t bo = ci == 0 ? boff.v[0] : ci == 1 ? boff.v[1] : ci == 2 ? boff.v[2] : ci == 3 ? boff.v[3] : 0u;
   uint32_t carry = 0;
   for (uint32_t w = 0; w < windows; w++) {
     const uint32_t bit = w * c;
@@ -174,7 +180,7 @@ __global__ __launch_bounds__(256) void recode_kernel(const uint64_t* __restrict_
     }
     const uint64_t at = ((uint64_t)w * gc + cl) * rc + r;
     keys[at] = mag ? ((cl * windows + w) * buckets + (mag - 1)) : sentinel;
-    vals[at] = (uint32_t)(r0 + r) | (neg << 31);
+    vals[at] = ((uint32_t)(r0 + r) + bo) | (neg << 31);
   }
 }
 
@@ -350,7 +356,8 @@ __global__ __launch_bounds__(64) void horner_kernel(const uint64_t* __restrict__
 
 template <class C, bool MONT>
 hipError_t run_msm(const MsmPlan& p, const uint64_t* d_scalars, uint64_t rows, uint64_t len, uint32_t n_cols,
-                   const uint64_t* d_bases, uint64_t* d_out, char* scr, int* sticky, hipStream_t s) {
+                   const uint64_t* d_bases, uint64_t* d_out, char* scr, int* sticky, hipStream_t s,
+                   const MsmBaseOffsets& boff) {
   uint32_t* keys_a = reinterpret_cast<uint32_t*>(scr + p.off_keys_a);
   uint32_t* keys_b = reinterpret_cast<uint32_t*>(scr + p.off_keys_b);
   uint32_t* vals_a = reinterpret_cast<uint32_t*>(scr + p.off_vals_a);
@@ -371,7 +378,7 @@ hipError_t run_msm(const MsmPlan& p, const uint64_t* d_scalars, uint64_t rows, u
       const uint32_t n = (uint32_t)n64;
       const uint64_t threads = (uint64_t)gc * rc;
       hipLaunchKernelGGL((recode_kernel<C, MONT>), dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, s, d_scalars,
-                         rows, r0, rc, col0, gc, p.c, p.windows, p.buckets, keys_a, vals_a);
+                         rows, r0, rc, col0, gc, p.c, p.windows, p.buckets, boff, keys_a, vals_a);
       if ((e = hipGetLastError()) != hipSuccess) return e;
       uint32_t end_bit = 1;
       while ((1ull << end_bit) <= n_buckets) end_bit++;  // the sentinel key n_buckets sorts too
@@ -413,12 +420,17 @@ hipError_t run_msm(const MsmPlan& p, const uint64_t* d_scalars, uint64_t rows, u
 
 hipError_t launch_msm(const MsmPlan& plan, const uint64_t* d_scalars, uint64_t rows, uint64_t len, uint32_t n_cols,
                       const uint64_t* d_bases, uint32_t form, uint64_t* d_out, void* scratch, int* sticky,
-                      hipStream_t s) {
+                      hipStream_t s, const MsmBaseOffsets* base_offsets) {
   hipError_t e = hipSuccess;
+  MsmBaseOffsets boff = {{0, 0, 0, 0}};
+  if (base_offsets) {
+    if (n_cols > MSM_OFFSET_COLS) return hipErrorInvalidValue;
+    boff = *base_offsets;
+  }
   field::with_curve_form(form, [&](auto c, auto mont) {
     using C = decltype(c);
     e = run_msm<C, decltype(mont)::value>(plan, d_scalars, rows, len, n_cols, d_bases, d_out, (char*)scratch, sticky,
-                                          s);
+                                          s, boff);
   });
   return e;
 }

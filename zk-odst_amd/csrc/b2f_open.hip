@@ -82,8 +82,7 @@ __global__ __launch_bounds__(OP_THREADS) void pow_table_kernel(uint64_t* tab, co
   const uint64_t pt = g / (OP_THREADS + 1);
   const uint32_t t = (uint32_t)(g % (OP_THREADS + 1));
   if (pt >= n_points) return;
-  const Fe z = to_mont<F>(load(pts + 4ull * pt));
-  Fe v = fe_pow<F>(z, t);
+  Fe v = pow_entry<F>(load(pts + 4ull * pt), t);
   store(tab + 4ull * (pt * OP_PW + t), v);
   if (t == OP_THREADS) {
     v = mul<F>(v, v);
