@@ -19,7 +19,19 @@
  * every stream-ordered call reuses, so two `*_dev` calls of one context in flight on two
  * streams race on it. Use one context per concurrent stream. `*_dev` calls are
  * stream-ordered and asynchronous; b2f_sync() waits and returns any device-side error raised
- * since the previous b2f_sync (errors are sticky until then). Host-pointer calls block. No
+ * since the previous b2f_sync (errors are sticky until then). Host-pointer calls block.
+ * Everything a context owns -- scratch, the cached domain tables, the pinned staging blocks, the
+ * status words -- is ordered by the stream its calls were issued on and by nothing else: the
+ * library never orders one caller stream behind another, and a stream created non-blocking is
+ * not ordered behind the null stream either. To move a context from stream A to stream B, call
+ * b2f_sync(ctx, A) after the last call on A and before the first call on B (any other wait for
+ * A's completion serves, but only b2f_sync collects A's errors); the cached tables and warm
+ * scratch are then used on B as they are. b2f_sync takes the stream the calls were issued on:
+ * it waits for that stream alone, then reads and clears the error word from the host, so no
+ * call of the context may be in flight on any stream while it runs. A call may block the host
+ * where its comment says so: when a context-owned block has to grow (it waits for `stream`
+ * first), and until the previous call's staged upload has run (the permutation and the
+ * evaluation / opening calls stage their host arrays in one pinned block each). No
  * call aborts; errors come back as B2F_* status codes with a message in b2f_last_error().
  * They map onto halo2's plonk::Error at a Rust call site: B2F_ERR_ROWS ->
  * NotEnoughRowsAvailable, the others -> Synthesis.
