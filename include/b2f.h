@@ -632,6 +632,61 @@ B2F_API int b2f_msm_dev(b2f_ctx* ctx, const uint64_t* d_scalars, uint64_t rows, 
 B2F_API int b2f_msm_plan(uint64_t len, uint32_t n_cols, uint32_t form, uint32_t* window_bits,
                          uint32_t* windows, uint32_t* group, uint64_t* scratch_bytes);
 
+/* Commitments of columns cut from u32 cells where they lie: the advice columns of the trace and the
+ * packed fixed column. halo2 commits an advice column in Lagrange form (commit_lagrange against
+ * g_lagrange), so the scalars are the raw cells followed by the blinding rows the caller drew; a
+ * cell of `bits` bits is ceil((bits + 1) / c) signed c-bit digits where a field element is
+ * ceil(256 / c), and nothing is widened to 32 bytes on the way.
+ * One column is a b2f_cell_column: scalar i (i < len) is
+ *   i < avail ? (d_cells[offset + i] >> shift) & (2^bits - 1) : 0
+ * Cells have no form: they are integers. d_tail (may be null, then tail_rows == 0; tail_rows <= 64)
+ * is a block d[(c * tail_rows + t) * 4 + limb] of full scalars in `form`, reduced, multiplying bases
+ * len .. len + tail_rows - 1. `form`, d_bases and d_out are as b2f_msm_dev defines them: n_cols affine
+ * points out, bit-exact. h_cols is a HOST array of n_cols b2f_cell_column (passed as void*: 24 bytes
+ * each); the call copies what it needs before it returns, so the caller may overwrite or free it at
+ * once. The passes are b2f_msm_dev's (sort, levelled bucket reduction, window sums) over each
+ * column's own windows, then windows * c doublings of Horner per column; the tail's scalar
+ * multiplications run on a side stream of the context beside them and are joined back before the one
+ * affine conversion. Asynchronous on `stream`; scratch is the context's (b2f_msm_cells_plan reports
+ * it); one B2F_KERNEL_QUOTIENT region per call. Errors, nothing launched and the next good call
+ * works: B2F_ERR_ARG for a null or misaligned pointer (d_cells, d_bases, d_out, d_tail 16-byte
+ * aligned), form > 3, len == 0 or len > 2^28, n_cols == 0 or n_cols > 4096, tail_rows > 64, d_tail
+ * non-null with tail_rows == 0 or the reverse, bits == 0, bits > 32 or shift + bits > 32, d_out
+ * overlapping an input; B2F_ERR_ROWS for offset + min(avail, len) > n_cells in any column or
+ * len + tail_rows > n_bases; B2F_ERR_HIP for runtime failures, scratch growth included. */
+typedef struct {
+  uint64_t offset; /* index of the column's first cell in d_cells */
+  uint64_t avail;  /* cells from `avail` on read as zero and are never loaded */
+  uint32_t shift;  /* 0..31 */
+  uint32_t bits;   /* 1..32, shift + bits <= 32 */
+} b2f_cell_column; /* 24 bytes */
+/* out[c] = sum_{i < len} scalar_c(i) base[i] + sum_{t < tail_rows} tail[c][t] base[len + t] */
+B2F_API int b2f_msm_cells_dev(b2f_ctx* ctx, const uint32_t* d_cells, uint64_t n_cells,
+                              const void* h_cols, uint32_t n_cols, uint64_t len,
+                              const uint64_t* d_tail, uint64_t tail_rows,
+                              const uint64_t* d_bases, uint64_t n_bases, uint32_t form,
+                              uint64_t* d_out, void* stream);
+/* host only: the plan b2f_msm_cells_dev would use: the window bits, the digits it recodes (len times
+ * the sum over the columns of ceil((bits + 1) / c)) and the scratch bytes; B2F_ERR_ARG where the call
+ * would refuse the descriptors, n_cols, len, tail_rows or form. Any output pointer may be null. */
+B2F_API int b2f_msm_cells_plan(const void* h_cols, uint32_t n_cols, uint64_t len,
+                               uint64_t tail_rows, uint32_t form, uint32_t* window_bits,
+                               uint64_t* digits, uint64_t* scratch_bytes);
+/* host only: the descriptors of one circuit's ten advice columns, the circuit being trace rows
+ * row_begin .. row_begin + usable_rows - 1 of a trace of total_rows rows (d_cells = d_advice,
+ * n_cells = 10 * total_rows), in halo2 column order: entry b2f_halo2_column_index(i) describes a_i
+ * (offset i * total_rows + row_begin, shift 0, bits 32). avail = min(usable_rows, total_rows -
+ * row_begin), 0 for row_begin >= total_rows: a circuit that runs past the trace reads zero rows there,
+ * as b2f_lookup_columns_dev defines. out10 holds 10 b2f_cell_column. Returns 10, or 0 (nothing
+ * written) for total_rows % 4 != 0, usable_rows == 0 or a null out10. */
+B2F_API uint32_t b2f_advice_cell_columns(uint64_t total_rows, uint64_t row_begin, uint64_t usable_rows,
+                                         void* out10);
+/* host only: the same for the B2F_NUM_FIXED_FP = 17 fixed columns over the packed fixed column
+ * (d_cells = d_fixed, n_cells = total_rows), in b2f_export_fixed_fp_dev's order: c < 16 selector bit
+ * c (shift c, bits 1), c = 16 k_0 (shift 16, bits 16); every offset is row_begin. Returns 17, or 0. */
+B2F_API uint32_t b2f_fixed_cell_columns(uint64_t total_rows, uint64_t row_begin, uint64_t usable_rows,
+                                        void* out17);
+
 /* The rounds of the inner product argument's opening (halo2's pasta backend:
  * poly/commitment/prover.rs::create_proof's loop) over three device vectors of length len = 2^j:
  * the coefficients p and the powers b, scalars d[i * 4 + limb] in `form` (any B2F_FP_*, reduced), and
@@ -692,7 +747,7 @@ B2F_API uint64_t b2f_gate_queries(uint32_t* pairs, uint64_t cap);
 #define B2F_KERNEL_PERM_SIGMA 7 /* permutation keygen: the sigma columns (b2f_permutation_sigma_dev) */
 #define B2F_KERNEL_NTT 8    /* NTT of prover columns (table build and all passes of one call) */
 #define B2F_KERNEL_QUOTIENT 9 /* quotient terms, the vanishing divide, the Lagrange selectors and the
-                                 evaluation / opening calls; the commitments (b2f_msm_dev);
+                                 evaluation / opening calls; the commitments (b2f_msm_dev, b2f_msm_cells_dev);
                                  the IPA rounds (b2f_ipa_*_dev) */
 #define B2F_NUM_KERNELS 10
 /* total_ms and count must each hold b2f_num_kernels() entries (= B2F_NUM_KERNELS of the

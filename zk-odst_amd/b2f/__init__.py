@@ -7,6 +7,6 @@ from ._lib import (FP_BN254_CANONICAL, FP_BN254_MONTGOMERY, FP_CANONICAL, FP_MON
                    NTT_FORWARD, NTT_INVERSE, B2FError, EvalReport, load)
 from .layout import (INPUT_DTYPE, SELECTORS, as_inputs, halo2_column_index, offsets,  # noqa: F401
                      parse_eip152, rows, split_fixed)
-from .engine import (DeviceBatch, Engine, copy_constraints, gate_queries,  # noqa: F401
-                     permutation_mapping)
+from .engine import (DeviceBatch, Engine, advice_cell_columns, copy_constraints,  # noqa: F401
+                     fixed_cell_columns, gate_queries, permutation_mapping)
 from . import curve, field  # noqa: F401

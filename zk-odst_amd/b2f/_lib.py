@@ -81,6 +81,22 @@ class EvalReport(ctypes.Structure):
 
 REPORT_BYTES = ctypes.sizeof(EvalReport)
 
+
+class CellColumn(ctypes.Structure):
+    """b2f_cell_column: one committed column cut from an array of u32 cells."""
+    _fields_ = [("offset", ctypes.c_uint64),
+                ("avail", ctypes.c_uint64),
+                ("shift", ctypes.c_uint32),
+                ("bits", ctypes.c_uint32)]
+
+
+def cell_columns(cols):
+    """A list of (offset, avail, shift, bits) -> a ctypes array of b2f_cell_column."""
+    arr = (CellColumn * len(cols))()
+    for d, (offset, avail, shift, bits) in zip(arr, cols):
+        d.offset, d.avail, d.shift, d.bits = int(offset), int(avail), int(shift), int(bits)
+    return arr
+
 # (name, restype, argtypes) for every function include/b2f.h declares.
 P = ctypes.c_void_p
 U64 = ctypes.c_uint64
@@ -137,6 +153,10 @@ SIGNATURES = [
     ("b2f_kate_divide_dev", I32, [P, P, U64, U64, ctypes.c_uint32, P, P, ctypes.c_uint32, P, U64, P]),
     ("b2f_msm_dev", I32, [P, P, U64, U64, ctypes.c_uint32, P, U64, ctypes.c_uint32, P, P]),
     ("b2f_msm_plan", I32, [U64, ctypes.c_uint32, ctypes.c_uint32, P, P, P, P]),
+    ("b2f_msm_cells_dev", I32, [P, P, U64, P, ctypes.c_uint32, U64, P, U64, P, U64, ctypes.c_uint32, P, P]),
+    ("b2f_msm_cells_plan", I32, [P, ctypes.c_uint32, U64, U64, ctypes.c_uint32, P, P, P]),
+    ("b2f_advice_cell_columns", ctypes.c_uint32, [U64, U64, U64, P]),
+    ("b2f_fixed_cell_columns", ctypes.c_uint32, [U64, U64, U64, P]),
     ("b2f_ipa_powers_dev", I32, [P, P, U64, ctypes.c_uint32, P, P]),
     ("b2f_ipa_round_dev", I32, [P, P, P, P, U64, ctypes.c_uint32, P, P, P]),
     ("b2f_ipa_fold_dev", I32, [P, P, P, P, U64, P, ctypes.c_uint32, P]),
@@ -233,6 +253,21 @@ def msm_plan(len_, n_cols, form=FP_MONTGOMERY, diag=False):
         raise B2FError(rc, "no msm plan for len = %d, n_cols = %d, form = %d" % (len_, n_cols, form))
     return {"window_bits": int(c.value), "windows": int(w.value), "group": int(g.value),
             "scratch_bytes": int(sb.value)}
+
+
+def msm_cells_plan(cols, len_, tail_rows=0, form=FP_MONTGOMERY, diag=False):
+    """Host only (b2f_msm_cells_plan): the plan b2f_msm_cells_dev would run for the columns `cols`
+    (a list of (offset, avail, shift, bits)), as a dict of window_bits, digits and scratch_bytes.
+    diag=True asks the diagnostics library, which honours B2F_DIAG_MSM_PLAN=c[,g].
+    B2FError(ERR_ARG) where the call would be refused."""
+    c, dg, sb = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    arr = cell_columns(cols)
+    rc = load(diag=diag).b2f_msm_cells_plan(arr, len(cols), int(len_), int(tail_rows), int(form), ctypes.byref(c),
+                                            ctypes.byref(dg), ctypes.byref(sb))
+    if rc != OK:
+        raise B2FError(rc, "no cell msm plan for %d columns, len = %d, tail_rows = %d, form = %d"
+                       % (len(cols), len_, tail_rows, form))
+    return {"window_bits": int(c.value), "digits": int(dg.value), "scratch_bytes": int(sb.value)}
 
 
 def ipa_direct_max_len(diag=False):

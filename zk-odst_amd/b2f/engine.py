@@ -556,6 +556,44 @@ class Engine:
                      out.data_ptr(), s)
         return out
 
+    def msm_cells_dev(self, d_cells, n_cells, cols, len_, d_tail, tail_rows, d_bases, n_bases, form, d_out,
+                      stream=0):
+        """b2f_msm_cells_dev: commitments of columns cut from u32 cells. cols: a list of (offset,
+        avail, shift, bits) or a ctypes array of _lib.CellColumn (copied by the call)."""
+        arr = cols if isinstance(cols, ctypes.Array) else _lib.cell_columns(cols)
+        self._check(self.lib.b2f_msm_cells_dev(self.ctx, _vp(d_cells), int(n_cells), arr, len(arr), int(len_),
+                                               _vp(d_tail), int(tail_rows), _vp(d_bases), int(n_bases),
+                                               int(form), _vp(d_out), _vp(stream)))
+
+    def msm_cells(self, cells, cols, bases, len, tail=None, form=_lib.FP_MONTGOMERY, out=None, stream=None):
+        """Commitments of columns where they lie (b2f_msm_cells_dev). cells: a contiguous int32 /
+        uint32 tensor (any shape: indexed flat); cols: a list of (offset, avail, shift, bits), scalar
+        i of a column being (cells[offset + i] >> shift) & (2^bits - 1) for i < avail and zero from
+        there to `len`; tail: int64 [n_cols, tail_rows, 4] full scalars in `form` multiplying bases
+        len .. len + tail_rows - 1 (the blinding rows), or None; bases: int64 [n_bases >= len +
+        tail_rows, 8]. Returns int64 [n_cols, 8] affine points, the identity all zeros."""
+        import torch
+
+        if cells.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not cells.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "msm_cells: cells must be a contiguous int32 / uint32 tensor")
+        if bases.dim() != 2 or bases.shape[1] != 8 or bases.dtype != torch.int64 or not bases.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "msm_cells: bases must be contiguous int64 [n_bases, 8]")
+        n_cols = builtins.len(cols)
+        tail_rows = 0
+        if tail is not None:
+            if tail.dim() != 3 or tail.shape[0] != n_cols or tail.shape[2] != 4 or tail.dtype != torch.int64 \
+                    or not tail.is_contiguous():
+                raise _lib.B2FError(_lib.ERR_ARG, "msm_cells: tail must be contiguous int64 [n_cols, tail_rows, 4]")
+            tail_rows = int(tail.shape[1])
+        if out is None:
+            out = torch.empty((n_cols, 8), dtype=torch.int64, device=cells.device)
+        if out.dim() != 2 or tuple(out.shape) != (n_cols, 8) or out.dtype != torch.int64 or not out.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "msm_cells: out must be contiguous int64 [n_cols, 8]")
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.msm_cells_dev(cells.data_ptr(), cells.numel(), cols, len, tail.data_ptr() if tail_rows else 0,
+                           tail_rows, bases.data_ptr(), int(bases.shape[0]), form, out.data_ptr(), s)
+        return out
+
     # ---------------------------------------------------------------- IPA opening rounds
     def ipa_powers_dev(self, x, len_, form, d_b, stream=0):
         """b2f_ipa_powers_dev: d_b[i] = x^i for i < len, in `form`; x a Python int (canonical)."""
@@ -727,6 +765,26 @@ def gate_queries():
     return out
 
 
+def _cell_columns(fn, n, total_rows, row_begin, usable_rows):
+    arr = (_lib.CellColumn * n)()
+    if int(fn(int(total_rows), int(row_begin), int(usable_rows), arr)) != n:
+        raise _lib.B2FError(_lib.ERR_ARG, "cell columns: total_rows %d is no multiple of 4 or usable_rows %d is 0"
+                            % (total_rows, usable_rows))
+    return [(int(d.offset), int(d.avail), int(d.shift), int(d.bits)) for d in arr]
+
+
+def advice_cell_columns(total_rows, row_begin, usable_rows):
+    """The ten (offset, avail, shift, bits) descriptors of one circuit's advice columns over the
+    trace's advice block, in halo2 column order (b2f_advice_cell_columns)."""
+    return _cell_columns(_lib.load().b2f_advice_cell_columns, _lib.NUM_ADVICE, total_rows, row_begin, usable_rows)
+
+
+def fixed_cell_columns(total_rows, row_begin, usable_rows):
+    """The seventeen descriptors of one circuit's fixed columns over the packed fixed column:
+    selector bits 0..15, then k_0 (b2f_fixed_cell_columns)."""
+    return _cell_columns(_lib.load().b2f_fixed_cell_columns, _lib.NUM_FIXED_FP, total_rows, row_begin, usable_rows)
+
+
 class DeviceBatch:
     """A batch resident on one GPU: inputs, offsets, the trace and the outputs, as torch
     tensors (int32/int64 storage holding u32/u64 bit patterns)."""
@@ -844,6 +902,26 @@ class DeviceBatch:
         eng.export_fixed_fp_dev(self.fixed.data_ptr(), self.total_rows, row_begin, nrows, form,
                                 out.data_ptr(), out.shape[1], s)
         return out
+
+    def commit_advice(self, eng, row_begin, usable_rows, bases, tail=None, form=_lib.FP_MONTGOMERY,
+                      stream=None):
+        """Commitments of the advice columns of circuits cut from the trace, read where the fill
+        left them (b2f_msm_cells_dev): halo2's commit_lagrange of each column against `bases`
+        (g_lagrange: int64 [n_bases, 8]), the scalars being rows row_begin .. + usable_rows - 1 and
+        then `tail` (int64 [n_columns, tail_rows, 4] in `form`: the blinding rows). row_begin: an
+        int (10 points out), or a list of ints: all the circuits in one call, circuit c's halo2
+        column h at output c * 10 + h. Returns int64 [10 * n_circuits, 8]."""
+        begins = [row_begin] if isinstance(row_begin, (int, np.integer)) else list(row_begin)
+        cols = []
+        for rb in begins:
+            cols += advice_cell_columns(self.total_rows, rb, usable_rows)
+        return eng.msm_cells(self.advice, cols, bases, usable_rows, tail=tail, form=form, stream=stream)
+
+    def commit_fixed(self, eng, row_begin, usable_rows, bases, form=_lib.FP_MONTGOMERY, stream=None):
+        """Commitments of one circuit's seventeen fixed columns (keygen), read from the packed
+        fixed column in export_fixed_fp's order. Returns int64 [17, 8]."""
+        cols = fixed_cell_columns(self.total_rows, row_begin, usable_rows)
+        return eng.msm_cells(self.fixed, cols, bases, usable_rows, form=form, stream=stream)
 
     def lookup_columns(self, eng, row_begin, usable_rows, theta, beta, gamma,
                        form=_lib.FP_MONTGOMERY, stream=None):

@@ -797,6 +797,124 @@ B2F_API int b2f_msm_dev(b2f_ctx* ctx, const uint64_t* d_scalars, uint64_t rows, 
 }  // extern "C"
 
 namespace {
+// The plan of a cell commitment: B2F_OK, or the code the call refuses its counts, descriptors or
+// (diagnostics library) forced plan with.
+int msm_cells_plan_for(const void* h_cols, uint32_t n_cols, uint64_t len, uint64_t tail_rows, uint32_t form,
+                       CellsPlan* plan) {
+  if (!h_cols || form > B2F_FP_BN254_MONTGOMERY || tail_rows > 64) return B2F_ERR_ARG;
+  uint32_t fc = 0, fg = 0;
+#ifdef B2F_DIAG
+  if (diag_msm_plan(&fc, &fg) < 0) return B2F_ERR_ARG;
+#endif
+  return msm_cells_plan_of(static_cast<const b2f_cell_column*>(h_cols), n_cols, len, fc, fg, plan) ? B2F_OK
+                                                                                                    : B2F_ERR_ARG;
+}
+
+uint32_t cell_columns(uint64_t total_rows, uint64_t row_begin, uint64_t usable_rows, void* out, uint32_t n,
+                      bool advice) {
+  if (!out || total_rows % 4 != 0 || usable_rows == 0) return 0;
+  const uint64_t left = row_begin >= total_rows ? 0 : total_rows - row_begin;
+  b2f_cell_column* cols = static_cast<b2f_cell_column*>(out);
+  for (uint32_t i = 0; i < n; i++) {
+    b2f_cell_column& d = cols[advice ? (uint32_t)b2f_halo2_column_index((int)i) : i];
+    d.offset = (advice ? i * total_rows : 0) + row_begin;
+    d.avail = usable_rows < left ? usable_rows : left;
+    d.shift = advice ? 0 : i;
+    d.bits = advice ? 32 : i < 16 ? 1 : 16;
+  }
+  return n;
+}
+}  // namespace
+
+extern "C" {
+
+B2F_API uint32_t b2f_advice_cell_columns(uint64_t total_rows, uint64_t row_begin, uint64_t usable_rows,
+                                         void* out10) {
+  return cell_columns(total_rows, row_begin, usable_rows, out10, B2F_NUM_ADVICE, true);
+}
+
+B2F_API uint32_t b2f_fixed_cell_columns(uint64_t total_rows, uint64_t row_begin, uint64_t usable_rows,
+                                        void* out17) {
+  return cell_columns(total_rows, row_begin, usable_rows, out17, B2F_NUM_FIXED_FP, false);
+}
+
+B2F_API int b2f_msm_cells_plan(const void* h_cols, uint32_t n_cols, uint64_t len, uint64_t tail_rows,
+                               uint32_t form, uint32_t* window_bits, uint64_t* digits, uint64_t* scratch_bytes) {
+  CellsPlan plan;
+  if (int rc = msm_cells_plan_for(h_cols, n_cols, len, tail_rows, form, &plan)) return rc;
+  if (window_bits) *window_bits = plan.c;
+  if (digits) *digits = plan.digits;
+  if (scratch_bytes) *scratch_bytes = plan.scratch_bytes;
+  return B2F_OK;
+}
+
+B2F_API int b2f_msm_cells_dev(b2f_ctx* ctx, const uint32_t* d_cells, uint64_t n_cells, const void* h_cols,
+                              uint32_t n_cols, uint64_t len, const uint64_t* d_tail, uint64_t tail_rows,
+                              const uint64_t* d_bases, uint64_t n_bases, uint32_t form, uint64_t* d_out,
+                              void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "msm cells";
+  if (!d_cells || !h_cols || !d_bases || !d_out) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (((uintptr_t)d_cells | (uintptr_t)d_bases | (uintptr_t)d_out | (uintptr_t)d_tail) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "%s: buffers must be 16-byte aligned", what);
+  if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "%s: unknown form %u", what, form);
+  if (len == 0 || len > (1ull << 28))
+    return set_err(ctx, B2F_ERR_ARG, "%s: len %llu not in [1, 2^28]", what, (unsigned long long)len);
+  if (n_cols == 0 || n_cols > 4096) return set_err(ctx, B2F_ERR_ARG, "%s: n_cols %u not in [1, 4096]", what, n_cols);
+  if (tail_rows > 64) return set_err(ctx, B2F_ERR_ARG, "%s: tail_rows %llu > 64", what, (unsigned long long)tail_rows);
+  if ((d_tail != nullptr) != (tail_rows != 0))
+    return set_err(ctx, B2F_ERR_ARG, "%s: d_tail and tail_rows must be given together", what);
+  if (n_cells > (1ull << 60) || n_bases > (1ull << 57))
+    return set_err(ctx, B2F_ERR_ARG, "%s: a block overflows the address space", what);
+  CellsPlan plan;
+  if (msm_cells_plan_for(h_cols, n_cols, len, tail_rows, form, &plan) != B2F_OK)
+    return set_err(ctx, B2F_ERR_ARG, "%s: a column's shift / bits out of range (bits 1..32, shift + bits <= 32), or a "
+                   "forced plan that is malformed or exceeds a pass", what);
+  const b2f_cell_column* cols = static_cast<const b2f_cell_column*>(h_cols);
+  for (uint32_t i = 0; i < n_cols; i++)
+    if (cols[i].offset > n_cells || plan.image[i].avail > n_cells - cols[i].offset)
+      return set_err(ctx, B2F_ERR_ROWS, "%s: column %u reads cells [%llu, +%u) of %llu", what, i,
+                     (unsigned long long)cols[i].offset, plan.image[i].avail, (unsigned long long)n_cells);
+  if (len + tail_rows > n_bases)
+    return set_err(ctx, B2F_ERR_ROWS, "%s: len + tail_rows %llu > n_bases", what, (unsigned long long)(len + tail_rows));
+  if (ranges_overlap(d_out, 64ull * n_cols, d_cells, 4 * n_cells) ||
+      ranges_overlap(d_out, 64ull * n_cols, d_bases, n_bases * 64) ||
+      (d_tail && ranges_overlap(d_out, 64ull * n_cols, d_tail, 32ull * n_cols * tail_rows)))
+    return set_err(ctx, B2F_ERR_ARG, "%s: the output overlaps an input", what);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (tail_rows)
+    if (int rc = ensure_side(ctx)) return rc;
+  // the descriptors: staged in pinned memory (rewritten once the previous call's upload is done),
+  // uploaded on the stream into the scratch, so h_cols is the caller's again when the call returns
+  const size_t image_bytes = sizeof(CellColumn) * (size_t)n_cols;
+  if (ctx->cells_ev_live) {
+    HIPCHK(ctx, hipEventSynchronize(ctx->cells_ev));
+    ctx->cells_ev_live = false;
+  }
+  if (!ctx->cells_ev) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->cells_ev, hipEventDisableTiming));
+  if (int rc = grow_pinned(ctx, &ctx->h_cells, &ctx->h_cells_cap, image_bytes, 1)) return rc;
+  if (int rc = grow_device(ctx, &ctx->d_msm, &ctx->msm_cap, plan.scratch_bytes, 1, s)) return rc;
+  memcpy(ctx->h_cells, plan.image.data(), image_bytes);
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, hipMemcpyAsync((char*)ctx->d_msm + plan.off_desc, ctx->h_cells, image_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipEventRecord(ctx->cells_ev, s));
+  ctx->cells_ev_live = true;
+  hipStream_t s2 = ctx->s2;
+#ifdef B2F_DIAG
+  // B2F_DIAG_MSM_TAIL=serial: the tail on the call's own stream (tools/bench_msm_cells.py --tail)
+  const char* tail_mode = getenv("B2F_DIAG_MSM_TAIL");
+  if (tail_mode && !strcmp(tail_mode, "serial")) s2 = s;
+#endif
+  HIPCHK(ctx, launch_msm_cells(plan, d_cells, n_cols, len, d_tail, (uint32_t)tail_rows, d_bases, form, d_out,
+                               ctx->d_msm, ctx->d_status + 2, s2, ctx->ev_fork, ctx->ev_join, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+}  // extern "C"
+
+namespace {
 // Host field helpers of the IPA fold: x R mod p of a canonical x (256 doublings mod p: p < 2^255,
 // so 2x never leaves four limbs) and x^-1 mod p by the divsteps of b2f_safegcd.h.
 void host_to_mont(uint32_t form, const uint64_t* x, uint64_t* out) {

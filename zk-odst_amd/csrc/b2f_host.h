@@ -89,6 +89,12 @@ struct b2f_ctx {
   size_t op_cap;
   void* d_msm;  // commitment scratch (b2f_msm.hip: msm_plan_of carves it)
   size_t msm_cap;
+  // b2f_msm_cells_dev: the call's column descriptors staged in pinned memory and uploaded
+  // asynchronously into d_msm (as the opening's plan is)
+  void* h_cells;
+  size_t h_cells_cap;  // in bytes
+  hipEvent_t cells_ev;
+  bool cells_ev_live;
   void* d_ipa;  // IPA round scratch beyond the commitments' (b2f_ipa.hip: ipa_scratch_bytes)
   size_t ipa_cap;
 };

@@ -1173,6 +1173,9 @@ B2F_API void b2f_destroy(b2f_ctx* ctx) {
   if (ctx->op_ev_live) (void)hipEventSynchronize(ctx->op_ev);
   if (ctx->op_ev) (void)hipEventDestroy(ctx->op_ev);
   (void)hipHostFree(ctx->h_op);
+  if (ctx->cells_ev_live) (void)hipEventSynchronize(ctx->cells_ev);
+  if (ctx->cells_ev) (void)hipEventDestroy(ctx->cells_ev);
+  (void)hipHostFree(ctx->h_cells);
   if (ctx->pm_inst_ev_live) (void)hipEventSynchronize(ctx->pm_inst_ev);
   if (ctx->pm_inst_ev) (void)hipEventDestroy(ctx->pm_inst_ev);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);

@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/b2f.h"
 
 namespace b2f {
@@ -109,6 +111,40 @@ hipError_t launch_msm(const MsmPlan& plan, const uint64_t* d_scalars, uint64_t r
 #ifdef B2F_DIAG
 int diag_msm_plan(uint32_t* c, uint32_t* g);
 #endif
+
+// b2f_msm.hip: the commitment of columns cut from u32 cells (b2f_msm_cells_dev). A column of
+// `bits` bits has ceil((bits + 1) / c) windows of its own; a pass takes a run of columns (a group)
+// and a chunk of rows, at most 2^24 digits and 2^20 buckets as above.
+struct CellColumn {  // the device image of one b2f_cell_column, 32 bytes
+  uint64_t offset;   // of the column's first cell
+  uint32_t avail;    // min(avail, len): rows from here on are zero and never loaded
+  uint32_t shift, mask;
+  uint32_t windows;  // ceil((bits + 1) / c)
+  uint32_t wbase;    // the column's first window among its group's
+  uint32_t pad;
+};
+struct CellsPlan {
+  uint32_t c, buckets;
+  uint64_t chunk;                 // rows per pass
+  uint64_t digits;                // len * (the sum of the columns' windows): what the call recodes
+  std::vector<uint32_t> first;    // group g is columns [first[g], first[g + 1])
+  std::vector<CellColumn> image;  // n_cols entries
+  uint64_t cap_entries, cap_buckets;
+  uint64_t off_keys_a, off_keys_b, off_vals_a, off_vals_b, off_sort, sort_bytes, off_pkey_a, off_pkey_b,
+      off_ppt_a, off_ppt_b, off_buckets, off_win, off_acc, off_tail, off_desc;
+  uint64_t scratch_bytes;
+};
+uint32_t msm_cells_default_window(uint64_t len, uint32_t bits);
+// false: a count or a descriptor out of range, or a forced plan that exceeds a pass
+bool msm_cells_plan_of(const b2f_cell_column* cols, uint32_t n_cols, uint64_t len, uint32_t force_c, uint32_t force_g,
+                       CellsPlan* plan);
+// The descriptors (plan.image) must already be at scratch + plan.off_desc, in stream order. With
+// tail_rows != 0 the tail's scalar multiplications run on s2 beside the cell passes (forked after
+// ev_fork, joined back into s through ev_join whatever the launches return).
+hipError_t launch_msm_cells(const CellsPlan& plan, const uint32_t* d_cells, uint32_t n_cols, uint64_t len,
+                            const uint64_t* d_tail, uint32_t tail_rows, const uint64_t* d_bases, uint32_t form,
+                            uint64_t* d_out, void* scratch, int* sticky, hipStream_t s2, hipEvent_t ev_fork,
+                            hipEvent_t ev_join, hipStream_t s);
 
 // b2f_ipa.hip: the IPA opening rounds. A round of len <= ipa_direct_max_len() is one direct launch;
 // a longer one is a two-column launch_msm with base offsets (its plan: msm_plan_of(len / 2, 2, ..),

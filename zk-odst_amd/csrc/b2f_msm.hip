@@ -32,6 +32,12 @@
 //   5. horner_kernel: one lane per column combines the windows (c doublings, one addition each),
 //      adds the pass into the column's accumulator and, after the last chunk, makes it affine
 //      with one inv_safegcd (B2F_ERR_CHECK through the sticky flag if that fails).
+//
+// b2f_msm_cells_dev commits columns cut from u32 cells (the trace's advice and fixed columns) with
+// the same steps 2 to 4 behind a front end of its own: recode_cells_kernel gives a column of `bits`
+// bits ceil((bits + 1) / c) windows where a field element has ceil(256 / c), horner_cells_kernel
+// runs over those windows alone, tail_kernel multiplies the call's few full scalars (the blinding
+// rows) out on a side stream, and finish_cells_kernel adds the two and makes the sum affine.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -354,19 +360,75 @@ __global__ __launch_bounds__(64) void horner_kernel(const uint64_t* __restrict__
   store_affine(out + (uint64_t)cl * 8, a);
 }
 
+// The scratch of a pass, carved by either plan (MsmPlan, CellsPlan: the same offsets by name).
+struct PassScratch {
+  uint32_t *keys_a, *keys_b, *vals_a, *vals_b;
+  void* sort;
+  uint64_t sort_bytes;
+  uint32_t* pkey[2];
+  uint64_t* ppt[2];
+  uint64_t *bucket, *win, *colacc;
+};
+template <class Plan>
+PassScratch carve(const Plan& p, char* scr) {
+  PassScratch m;
+  m.keys_a = reinterpret_cast<uint32_t*>(scr + p.off_keys_a);
+  m.keys_b = reinterpret_cast<uint32_t*>(scr + p.off_keys_b);
+  m.vals_a = reinterpret_cast<uint32_t*>(scr + p.off_vals_a);
+  m.vals_b = reinterpret_cast<uint32_t*>(scr + p.off_vals_b);
+  m.sort = scr + p.off_sort;
+  m.sort_bytes = p.sort_bytes;
+  m.pkey[0] = reinterpret_cast<uint32_t*>(scr + p.off_pkey_a);
+  m.pkey[1] = reinterpret_cast<uint32_t*>(scr + p.off_pkey_b);
+  m.ppt[0] = reinterpret_cast<uint64_t*>(scr + p.off_ppt_a);
+  m.ppt[1] = reinterpret_cast<uint64_t*>(scr + p.off_ppt_b);
+  m.bucket = reinterpret_cast<uint64_t*>(scr + p.off_buckets);
+  m.win = reinterpret_cast<uint64_t*>(scr + p.off_win);
+  m.colacc = reinterpret_cast<uint64_t*>(scr + p.off_acc);
+  return m;
+}
+
+// Steps 2 to 4 of a pass: the n digits in keys_a / vals_a, of n_windows (column, window) pairs of
+// `buckets` buckets each, become the n_windows window sums in m.win.
+template <class C>
+hipError_t sort_reduce_windows(const PassScratch& m, uint32_t n, uint32_t n_windows, uint32_t buckets,
+                               const uint64_t* d_bases, hipStream_t s) {
+  hipError_t e;
+  const uint32_t n_buckets = n_windows * buckets;
+  uint32_t end_bit = 1;
+  while ((1ull << end_bit) <= n_buckets) end_bit++;  // the sentinel key n_buckets sorts too
+  size_t need = 0;
+  e = rocprim::radix_sort_pairs((void*)nullptr, need, m.keys_a, m.keys_b, m.vals_a, m.vals_b, (size_t)n, 0, end_bit, s);
+  if (e != hipSuccess) return e;
+  if (need > m.sort_bytes) return hipErrorOutOfMemory;
+  need = m.sort_bytes;
+  e = rocprim::radix_sort_pairs(m.sort, need, m.keys_a, m.keys_b, m.vals_a, m.vals_b, (size_t)n, 0, end_bit, s);
+  if (e != hipSuccess) return e;
+  if ((e = hipMemsetAsync(m.bucket, 0, 128ull * n_buckets, s)) != hipSuccess) return e;
+  // level 0 reads the sorted digits; level l + 1 reads what level l wrote (ping-pong)
+  uint32_t nl = n, nseg = (n + SEG - 1) / SEG;
+  hipLaunchKernelGGL((reduce_kernel<C, true>), dim3((nseg + 127) / 128), dim3(128), 0, s, m.keys_b, m.vals_b,
+                     (const uint64_t*)nullptr, nl, d_bases, m.bucket, n_buckets, m.pkey[0], m.ppt[0]);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  int src = 0;
+  while (nseg > 1) {
+    nl = 2 * nseg;
+    nseg = (nl + SEG - 1) / SEG;
+    hipLaunchKernelGGL((reduce_kernel<C, false>), dim3((nseg + 127) / 128), dim3(128), 0, s, m.pkey[src],
+                       (const uint32_t*)nullptr, m.ppt[src], nl, (const uint64_t*)nullptr, m.bucket, n_buckets,
+                       m.pkey[src ^ 1], m.ppt[src ^ 1]);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    src ^= 1;
+  }
+  hipLaunchKernelGGL((window_kernel<C>), dim3(n_windows), dim3(WIN_THREADS), 0, s, m.bucket, buckets, m.win);
+  return hipGetLastError();
+}
+
 template <class C, bool MONT>
 hipError_t run_msm(const MsmPlan& p, const uint64_t* d_scalars, uint64_t rows, uint64_t len, uint32_t n_cols,
                    const uint64_t* d_bases, uint64_t* d_out, char* scr, int* sticky, hipStream_t s,
                    const MsmBaseOffsets& boff) {
-  uint32_t* keys_a = reinterpret_cast<uint32_t*>(scr + p.off_keys_a);
-  uint32_t* keys_b = reinterpret_cast<uint32_t*>(scr + p.off_keys_b);
-  uint32_t* vals_a = reinterpret_cast<uint32_t*>(scr + p.off_vals_a);
-  uint32_t* vals_b = reinterpret_cast<uint32_t*>(scr + p.off_vals_b);
-  uint32_t* pkey[2] = {reinterpret_cast<uint32_t*>(scr + p.off_pkey_a), reinterpret_cast<uint32_t*>(scr + p.off_pkey_b)};
-  uint64_t* ppt[2] = {reinterpret_cast<uint64_t*>(scr + p.off_ppt_a), reinterpret_cast<uint64_t*>(scr + p.off_ppt_b)};
-  uint64_t* bucket = reinterpret_cast<uint64_t*>(scr + p.off_buckets);
-  uint64_t* win = reinterpret_cast<uint64_t*>(scr + p.off_win);
-  uint64_t* colacc = reinterpret_cast<uint64_t*>(scr + p.off_acc);
+  const PassScratch m = carve(p, scr);
   hipError_t e;
   for (uint32_t col0 = 0; col0 < n_cols; col0 += p.group) {
     const uint32_t gc = n_cols - col0 < p.group ? n_cols - col0 : p.group;
@@ -375,45 +437,202 @@ hipError_t run_msm(const MsmPlan& p, const uint64_t* d_scalars, uint64_t rows, u
       const uint64_t n64 = (uint64_t)gc * rc * p.windows;
       const uint32_t n_buckets = gc * p.windows * p.buckets;
       if (n64 > p.cap_entries || n_buckets > p.cap_buckets) return hipErrorInvalidValue;  // the plan's own bound
-      const uint32_t n = (uint32_t)n64;
       const uint64_t threads = (uint64_t)gc * rc;
       hipLaunchKernelGGL((recode_kernel<C, MONT>), dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, s, d_scalars,
-                         rows, r0, rc, col0, gc, p.c, p.windows, p.buckets, boff, keys_a, vals_a);
+                         rows, r0, rc, col0, gc, p.c, p.windows, p.buckets, boff, m.keys_a, m.vals_a);
       if ((e = hipGetLastError()) != hipSuccess) return e;
-      uint32_t end_bit = 1;
-      while ((1ull << end_bit) <= n_buckets) end_bit++;  // the sentinel key n_buckets sorts too
-      size_t need = 0;
-      e = rocprim::radix_sort_pairs((void*)nullptr, need, keys_a, keys_b, vals_a, vals_b, (size_t)n, 0, end_bit, s);
-      if (e != hipSuccess) return e;
-      if (need > p.sort_bytes) return hipErrorOutOfMemory;
-      need = p.sort_bytes;
-      e = rocprim::radix_sort_pairs((void*)(scr + p.off_sort), need, keys_a, keys_b, vals_a, vals_b, (size_t)n, 0,
-                                    end_bit, s);
-      if (e != hipSuccess) return e;
-      if ((e = hipMemsetAsync(bucket, 0, 128ull * n_buckets, s)) != hipSuccess) return e;
-      // level 0 reads the sorted digits; level l + 1 reads what level l wrote (ping-pong)
-      uint32_t nl = n, nseg = (n + SEG - 1) / SEG;
-      hipLaunchKernelGGL((reduce_kernel<C, true>), dim3((nseg + 127) / 128), dim3(128), 0, s, keys_b, vals_b,
-                         (const uint64_t*)nullptr, nl, d_bases, bucket, n_buckets, pkey[0], ppt[0]);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-      int src = 0;
-      while (nseg > 1) {
-        nl = 2 * nseg;
-        nseg = (nl + SEG - 1) / SEG;
-        hipLaunchKernelGGL((reduce_kernel<C, false>), dim3((nseg + 127) / 128), dim3(128), 0, s, pkey[src],
-                           (const uint32_t*)nullptr, ppt[src], nl, (const uint64_t*)nullptr, bucket, n_buckets,
-                           pkey[src ^ 1], ppt[src ^ 1]);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        src ^= 1;
-      }
-      hipLaunchKernelGGL((window_kernel<C>), dim3(gc * p.windows), dim3(WIN_THREADS), 0, s, bucket, p.buckets, win);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-      hipLaunchKernelGGL((horner_kernel<C>), dim3((gc + 63) / 64), dim3(64), 0, s, win, gc, p.c, p.windows, colacc,
+      if ((e = sort_reduce_windows<C>(m, (uint32_t)n64, gc * p.windows, p.buckets, d_bases, s)) != hipSuccess) return e;
+      hipLaunchKernelGGL((horner_kernel<C>), dim3((gc + 63) / 64), dim3(64), 0, s, m.win, gc, p.c, p.windows, m.colacc,
                          r0 == 0 ? 1 : 0, r0 + rc >= len ? 1 : 0, d_out + (uint64_t)col0 * 8, sticky);
       if ((e = hipGetLastError()) != hipSuccess) return e;
     }
   }
   return hipSuccess;
+}
+
+// ---- the cell front end (b2f_msm_cells_dev) ----------------------------------------------------
+// 1'. One lane per (column of the group, row of the chunk); consecutive lanes read consecutive
+// cells. The column's scalar is its field of the cell, zero from `avail` on (never loaded); it
+// becomes the column's own `windows` signed digits in recode_kernel's encoding, at entries
+// (wbase + w) * rc + r with keys (wbase + w) * buckets + |d| - 1. windows * c >= bits + 1, so the
+// top window's digit is at most 2^(c-1) - 1 plus the carry: it never carries out.
+__global__ __launch_bounds__(256) void recode_cells_kernel(const uint32_t* __restrict__ cells,
+                                                           const CellColumn* __restrict__ cols, uint32_t r0,
+                                                           uint32_t rc, uint32_t gc, uint32_t c, uint32_t buckets,
+                                                           uint32_t sentinel, uint32_t* __restrict__ keys,
+                                                           uint32_t* __restrict__ vals) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (uint64_t)gc * rc) return;
+  const uint32_t cl = (uint32_t)(t / rc), r = (uint32_t)(t % rc);
+  const CellColumn d = cols[cl];
+  const uint32_t row = r0 + r;
+  uint64_t v = 0;  // 64 bits: the top window's shift may be 32
+  if (row < d.avail) v = (cells[d.offset + row] >> d.shift) & d.mask;
+  const uint32_t half = 1u << (c - 1);
+  uint32_t carry = 0;
+  for (uint32_t w = 0; w < d.windows; w++) {
+    const uint32_t raw = ((uint32_t)(v >> (w * c)) & ((1u << c) - 1)) + carry;
+    uint32_t mag, neg = 0;
+    if (raw > half) {  // d = raw - 2^c < 0, and the next window gets the 2^c back
+      mag = (1u << c) - raw;
+      neg = 1;
+      carry = 1;
+    } else {
+      mag = raw;
+      carry = 0;
+    }
+    const uint32_t at = (d.wbase + w) * rc + r;
+    keys[at] = mag ? ((d.wbase + w) * buckets + (mag - 1)) : sentinel;
+    vals[at] = row | (neg << 31);
+  }
+}
+
+// 5'. Horner over the column's own windows (windows * c doublings), added into the column's
+// accumulator; the affine conversion is finish_cells_kernel's, after the last pass and the tail.
+template <class C>
+__global__ __launch_bounds__(64) void horner_cells_kernel(const uint64_t* __restrict__ win,
+                                                          const CellColumn* __restrict__ cols, uint32_t gc, uint32_t c,
+                                                          uint64_t* __restrict__ colacc, int first) {
+  using F = typename C::Base;
+  const uint32_t cl = blockIdx.x * blockDim.x + threadIdx.x;
+  if (cl >= gc) return;
+  const CellColumn d = cols[cl];
+  Xyzz acc = xyzz_identity();
+#pragma unroll 1
+  for (uint32_t w = d.windows; w-- > 0;) {
+#pragma unroll 1
+    for (uint32_t k = 0; k < c; k++) acc = dbl<F>(acc);
+    acc = add<F>(acc, load_xyzz(win + (uint64_t)(d.wbase + w) * 16));
+  }
+  if (!first) acc = add<F>(acc, load_xyzz(colacc + (uint64_t)cl * 16));
+  store_xyzz(colacc + (uint64_t)cl * 16, acc);
+}
+
+// The tail: one wave per column, lane t the full-width product tail[col][t] * base[len + t]
+// (curve::scalar_mul), the lanes' points summed by an LDS tree into tailacc[col].
+constexpr uint32_t TAIL_MAX = 64;
+template <class C, bool MONT>
+__global__ __launch_bounds__(TAIL_MAX) void tail_kernel(const uint64_t* __restrict__ tail, uint32_t tail_rows,
+                                                        const uint64_t* __restrict__ bases,
+                                                        uint64_t* __restrict__ tailacc) {
+  using F = typename C::Base;
+  using FS = typename C::Scalar;
+  __shared__ uint32_t lds[TAIL_MAX][33];  // one XYZZ per lane, padded against bank conflicts
+  const uint32_t t = threadIdx.x;
+  Xyzz acc = xyzz_identity();
+  if (t < tail_rows) {
+    Fe k = load(tail + ((uint64_t)blockIdx.x * tail_rows + t) * 4);
+    if (MONT) k = to_canonical<FS>(k);
+    acc = scalar_mul<F>(load_affine(bases + (uint64_t)t * 8), k);
+  }
+  auto put = [&](const Xyzz& p) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      lds[t][i] = p.x.w[i];
+      lds[t][8 + i] = p.y.w[i];
+      lds[t][16 + i] = p.zz.w[i];
+      lds[t][24 + i] = p.zzz.w[i];
+    }
+  };
+  auto get = [&](uint32_t u) {
+    Xyzz p;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      p.x.w[i] = lds[u][i];
+      p.y.w[i] = lds[u][8 + i];
+      p.zz.w[i] = lds[u][16 + i];
+      p.zzz.w[i] = lds[u][24 + i];
+    }
+    return p;
+  };
+  put(acc);
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t s = TAIL_MAX / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      acc = add<F>(acc, get(t + s));
+      put(acc);
+    }
+    __syncthreads();
+  }
+  if (t == 0) store_xyzz(tailacc + (uint64_t)blockIdx.x * 16, acc);
+}
+
+// out[col] = affine(colacc[col] + tailacc[col]) (tailacc null: a call without a tail)
+template <class C>
+__global__ __launch_bounds__(64) void finish_cells_kernel(const uint64_t* __restrict__ colacc,
+                                                          const uint64_t* __restrict__ tailacc, uint32_t n_cols,
+                                                          uint64_t* __restrict__ out, int* sticky) {
+  using F = typename C::Base;
+  const uint32_t col = blockIdx.x * blockDim.x + threadIdx.x;
+  if (col >= n_cols) return;
+  Xyzz acc = load_xyzz(colacc + (uint64_t)col * 16);
+  if (tailacc) acc = add<F>(acc, load_xyzz(tailacc + (uint64_t)col * 16));
+  bool ok = true;
+  const Affine a = to_affine<F>(acc, ok);
+  if (!ok) atomicOr(sticky, 1 << B2F_ERR_CHECK);
+  store_affine(out + (uint64_t)col * 8, a);
+}
+
+// the passes over (group, row chunk): every column's accumulator ends in m.colacc[column]
+template <class C>
+hipError_t run_cell_passes(const CellsPlan& p, const PassScratch& m, const CellColumn* desc, const uint32_t* d_cells,
+                           uint64_t len, const uint64_t* d_bases, hipStream_t s) {
+  hipError_t e;
+  for (size_t g = 0; g + 1 < p.first.size(); g++) {
+    const uint32_t col0 = p.first[g], gc = p.first[g + 1] - col0;
+    const CellColumn& lastc = p.image[col0 + gc - 1];
+    const uint32_t n_windows = lastc.wbase + lastc.windows;
+    for (uint64_t r0 = 0; r0 < len; r0 += p.chunk) {
+      const uint32_t rc = (uint32_t)(len - r0 < p.chunk ? len - r0 : p.chunk);
+      const uint64_t n64 = (uint64_t)n_windows * rc, nb64 = (uint64_t)n_windows * p.buckets;
+      if (n64 > p.cap_entries || nb64 > p.cap_buckets) return hipErrorInvalidValue;  // the plan's own bound
+      const uint64_t threads = (uint64_t)gc * rc;
+      hipLaunchKernelGGL(recode_cells_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, s, d_cells,
+                         desc + col0, (uint32_t)r0, rc, gc, p.c, p.buckets, (uint32_t)nb64 | EMPTY, m.keys_a, m.vals_a);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+      if ((e = sort_reduce_windows<C>(m, (uint32_t)n64, n_windows, p.buckets, d_bases, s)) != hipSuccess) return e;
+      hipLaunchKernelGGL((horner_cells_kernel<C>), dim3((gc + 63) / 64), dim3(64), 0, s, m.win, desc + col0, gc, p.c,
+                         m.colacc + (uint64_t)col0 * 16, r0 == 0 ? 1 : 0);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+  }
+  return hipSuccess;
+}
+
+template <class C, bool MONT>
+hipError_t run_msm_cells(const CellsPlan& p, const uint32_t* d_cells, uint32_t n_cols, uint64_t len,
+                         const uint64_t* d_tail, uint32_t tail_rows, const uint64_t* d_bases, uint64_t* d_out,
+                         char* scr, int* sticky, hipStream_t s2, hipEvent_t ev_fork, hipEvent_t ev_join,
+                         hipStream_t s) {
+  const PassScratch m = carve(p, scr);
+  const CellColumn* desc = reinterpret_cast<const CellColumn*>(scr + p.off_desc);
+  uint64_t* tailacc = reinterpret_cast<uint64_t*>(scr + p.off_tail);
+  hipError_t e = hipSuccess;
+  bool forked = false;
+  if (tail_rows) {
+    // the tail's 255-doubling chains run on s2 beside the cell passes; they read only the caller's
+    // tail and bases and write tailacc, which nothing else touches before the join (s2 == s: the
+    // diagnostics library's serial form, the overlap's A/B)
+    if (s2 != s) {
+      if ((e = hipEventRecord(ev_fork, s)) != hipSuccess) return e;
+      if ((e = hipStreamWaitEvent(s2, ev_fork, 0)) != hipSuccess) return e;
+      forked = true;
+    }
+    hipLaunchKernelGGL((tail_kernel<C, MONT>), dim3(n_cols), dim3(TAIL_MAX), 0, s2, d_tail, tail_rows,
+                       d_bases + len * 8, tailacc);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = run_cell_passes<C>(p, m, desc, d_cells, len, d_bases, s);
+  if (forked) {  // on every path: s2 never runs on past the call
+    hipError_t j = hipEventRecord(ev_join, s2);
+    if (j == hipSuccess) j = hipStreamWaitEvent(s, ev_join, 0);
+    if (e == hipSuccess) e = j;
+  }
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((finish_cells_kernel<C>), dim3((n_cols + 63) / 64), dim3(64), 0, s, m.colacc,
+                     tail_rows ? tailacc : (const uint64_t*)nullptr, n_cols, d_out, sticky);
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -435,10 +654,111 @@ hipError_t launch_msm(const MsmPlan& plan, const uint64_t* d_scalars, uint64_t r
   return e;
 }
 
+uint32_t msm_cells_default_window(uint64_t len, uint32_t bits) {
+  // The fewest windows a width the length can afford gives, at the narrowest width that gives them:
+  // the digits (sorted and added) go with the windows, the buckets (cleared and summed) with 2^c.
+  // The widest affordable width is floor((log2 len + 2) / 2), in [3, 16]: 9 at 2^17, 11 at 2^20.
+  // A 32-bit cell is then 4 windows of 9 bits at 2^17 rows and 3 of 11 at 2^20, a 16-bit limb 2 of
+  // 9, a selector bit 1 of 2: the fastest width of the sweep in each of its eight rows (DESIGN.md
+  // 4.9, tools/bench_msm_cells.py --sweep).
+  uint32_t cmax = (log2_floor(len) + 2) / 2;
+  cmax = cmax < 3 ? 3 : cmax > 16 ? 16 : cmax;
+  const uint32_t wmin = (bits + 1 + cmax - 1) / cmax;
+  return (bits + 1 + wmin - 1) / wmin;
+}
+
+bool msm_cells_plan_of(const b2f_cell_column* cols, uint32_t n_cols, uint64_t len, uint32_t force_c, uint32_t force_g,
+                       CellsPlan* p) {
+  if (!cols || len == 0 || len > (1ull << 28) || n_cols == 0 || n_cols > 4096 || force_c > 16) return false;
+  uint32_t max_bits = 0;
+  for (uint32_t i = 0; i < n_cols; i++) {
+    if (cols[i].bits == 0 || cols[i].bits > 32 || cols[i].shift > 31 || cols[i].shift + cols[i].bits > 32) return false;
+    if (cols[i].bits > max_bits) max_bits = cols[i].bits;
+  }
+  const uint32_t c = force_c ? force_c : msm_cells_default_window(len, max_bits);
+  p->c = c;
+  p->buckets = 1u << (c - 1);
+  p->image.assign(n_cols, CellColumn());
+  uint64_t sum_w = 0;
+  uint32_t max_w = 0;
+  for (uint32_t i = 0; i < n_cols; i++) {
+    CellColumn& d = p->image[i];
+    d.offset = cols[i].offset;
+    d.avail = (uint32_t)(cols[i].avail < len ? cols[i].avail : len);
+    d.shift = cols[i].shift;
+    d.mask = cols[i].bits == 32 ? 0xffffffffu : (1u << cols[i].bits) - 1;
+    d.windows = (cols[i].bits + 1 + c - 1) / c;  // the field's bits and the recoding carry
+    d.pad = 0;
+    sum_w += d.windows;
+    if (d.windows > max_w) max_w = d.windows;
+  }
+  p->digits = len * sum_w;
+  // a chunk of rows holds the widest column; a group is a run of columns whose windows fit the pass
+  uint64_t chunk = CAP_ENTRIES / max_w;
+  if (chunk > len) chunk = len;
+  p->chunk = chunk;
+  uint64_t wcap = CAP_ENTRIES / chunk;
+  if (wcap > CAP_BUCKETS / p->buckets) wcap = CAP_BUCKETS / p->buckets;
+  if (max_w > wcap) return false;
+  p->first.assign(1, 0);
+  uint32_t w = 0, count = 0;
+  for (uint32_t i = 0; i < n_cols; i++) {
+    if (count && (w + p->image[i].windows > wcap || (force_g && count == force_g))) {
+      p->first.push_back(i);
+      w = count = 0;
+    }
+    p->image[i].wbase = w;
+    w += p->image[i].windows;
+    count++;
+  }
+  p->first.push_back(n_cols);
+  // Scratch, by bounds that do not shrink as len or n_cols grows (as msm_plan_of's): the call's
+  // digits at len rounded up to a power of two and all its windows' buckets, capped by the pass
+  uint64_t e = (2ull << log2_floor(len)) * sum_w;
+  if (e > CAP_ENTRIES) e = CAP_ENTRIES;
+  p->cap_entries = e;
+  uint64_t bk = sum_w * p->buckets;
+  if (bk > CAP_BUCKETS) bk = CAP_BUCKETS;
+  p->cap_buckets = bk;
+  const uint64_t n1 = 2 * ((e + SEG - 1) / SEG), n2 = 2 * ((n1 + SEG - 1) / SEG);
+  uint64_t off = 0;
+  p->off_keys_a = off; off += align256(4 * e);
+  p->off_keys_b = off; off += align256(4 * e);
+  p->off_vals_a = off; off += align256(4 * e);
+  p->off_vals_b = off; off += align256(4 * e);
+  p->off_sort = off; p->sort_bytes = sort_temp_bound(e); off += p->sort_bytes;
+  p->off_pkey_a = off; off += align256(4 * n1);
+  p->off_pkey_b = off; off += align256(4 * n2);
+  p->off_ppt_a = off; off += align256(128 * n1);
+  p->off_ppt_b = off; off += align256(128 * n2);
+  p->off_buckets = off; off += align256(128 * bk);
+  p->off_win = off; off += align256(128 * (sum_w < CAP_BUCKETS ? sum_w : CAP_BUCKETS));
+  p->off_acc = off; off += align256(128ull * n_cols);
+  p->off_tail = off; off += align256(128ull * n_cols);
+  p->off_desc = off; off += align256(sizeof(CellColumn) * (uint64_t)n_cols);
+  p->scratch_bytes = off;
+  return true;
+}
+
+hipError_t launch_msm_cells(const CellsPlan& plan, const uint32_t* d_cells, uint32_t n_cols, uint64_t len,
+                            const uint64_t* d_tail, uint32_t tail_rows, const uint64_t* d_bases, uint32_t form,
+                            uint64_t* d_out, void* scratch, int* sticky, hipStream_t s2, hipEvent_t ev_fork,
+                            hipEvent_t ev_join, hipStream_t s) {
+  if (tail_rows > TAIL_MAX) return hipErrorInvalidValue;
+  hipError_t e = hipSuccess;
+  field::with_curve_form(form, [&](auto c, auto mont) {
+    using C = decltype(c);
+    e = run_msm_cells<C, decltype(mont)::value>(plan, d_cells, n_cols, len, d_tail, tail_rows, d_bases, d_out,
+                                                (char*)scratch, sticky, s2, ev_fork, ev_join, s);
+  });
+  return e;
+}
+
 #ifdef B2F_DIAG
 // Diagnostics build only: B2F_DIAG_MSM_PLAN=c[,g] read at the call forces the window width
-// (1..16) and, optionally, the column group (1..4096) of b2f_msm_dev / b2f_msm_plan
-// (tests/test_gpu_msm.py: widths the product never picks at small lengths). 0: unset; 1: *c and *g
+// (1..16) and, optionally, the column group (1..4096) of b2f_msm_dev / b2f_msm_plan and of
+// b2f_msm_cells_dev / b2f_msm_cells_plan (tests/test_gpu_msm.py, tests/test_gpu_msm_cells.py: widths
+// the product never picks at small lengths). 0: unset; 1: *c and *g
 // (0: not given) hold the forced plan; -1: anything else (decimal digits only, no sign, space or
 // leading zero). There is no fallback: the caller refuses the call on -1.
 int diag_msm_plan(uint32_t* c, uint32_t* g) {
