@@ -77,6 +77,45 @@ def test_chain_inputs_errors(engine):
                             out.data_ptr())  # n = 0: nothing to do
 
 
+@pytest.mark.parametrize("rounds", [0, 13])
+def test_chain_inputs_records(engine, rounds):
+    """b2f_chain_inputs_dev's records field by field against a numpy construction of b2f_input,
+    on inputs no digest test reaches: t[1] = 2^64 - 1, t[0] past 2^32, f in {0, 1, 2, 0xffffffff}
+    (non-zero stores 1), rounds 0 and 13. The 216-byte record has no padding (the header's fields
+    are naturally aligned and fill it): every byte of the output is a field's, so the whole buffer
+    is compared, over a poisoned output."""
+    import torch
+
+    import b2f
+
+    n = 5
+    rng = np.random.default_rng(216 + rounds)
+    h = rng.integers(0, 2**64, (n, 8), dtype=np.uint64)
+    m = rng.integers(0, 2**64, (n, 16), dtype=np.uint64)
+    t = np.array([[2**32 + 5, 2**64 - 1], [2**64 - 1, 2**64 - 1], [2**63, 0], [0, 2**64 - 1],
+                  [2**32 - 1, 1]], dtype=np.uint64)
+    f = np.array([0, 1, 2, 0xffffffff, 0], dtype=np.uint32)
+    want = np.zeros(n, dtype=b2f.INPUT_DTYPE)
+    want["h"], want["m"], want["t"] = h, m, t
+    want["rounds"] = rounds
+    want["f"] = [0, 1, 1, 1, 0]
+    assert b2f.INPUT_DTYPE.itemsize == 216 == 8 * 8 + 16 * 8 + 2 * 8 + 4 + 4
+    assert [b2f.INPUT_DTYPE.fields[k][1] for k in ("h", "m", "t", "rounds", "f")] == [0, 64, 192, 208, 212]
+
+    dev = torch.device("cuda:0")
+    up = lambda a, dt: torch.from_numpy(a.view(dt).copy()).to(dev)  # noqa: E731
+    d_h, d_m, d_t, d_f = up(h, np.int64), up(m, np.int64), up(t, np.int64), up(f, np.int32)
+    out = torch.full(((n + 1) * 216,), 0xa5, dtype=torch.uint8, device=dev)
+    engine.chain_inputs_dev(d_h.data_ptr(), d_m.data_ptr(), d_t.data_ptr(), d_f.data_ptr(), rounds, n,
+                            out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    raw = out.cpu().numpy()
+    got = np.frombuffer(raw[:n * 216].tobytes(), dtype=b2f.INPUT_DTYPE)
+    for field in ("h", "m", "t", "rounds", "f"):
+        assert np.array_equal(got[field], want[field]), field
+    assert raw[:n * 216].tobytes() == want.tobytes()
+    assert (raw[n * 216:] == 0xa5).all(), "a record past n was written"
+
+
 @pytest.mark.parametrize("use_side_stream", [False, True])
 def test_split_right_after_fused_without_host_sync(engine, use_side_stream):
     """run_plan once needed a host synchronize between torch's copies/allocations
