@@ -601,9 +601,9 @@ B2F_API int b2f_kate_divide_dev(b2f_ctx* ctx, const uint64_t* d_cols, uint64_t r
 /* The commitments: a batched variable-base multi-scalar multiplication on the curve whose scalar
  * field `form` names: Vesta (y^2 = x^3 + 5 over pasta Fq, group order pasta Fp) for forms 0/1,
  * BN254 G1 (y^2 = x^3 + 3 over bn256::Fq, group order bn256::Fr) for forms 2/3. This is halo2's
- * commit / commit_lagrange of a column against the parameters' points (g, g_lagrange); building
- * those points, the blinding term's generator, the transcript and the IPA / KZG opening stay with
- * the caller.
+ * commit / commit_lagrange of a column against the parameters' points (g, g_lagrange);
+ * b2f_group_ntt_dev derives g_lagrange from g; choosing g, the blinding term's generator, the
+ * transcript and the IPA / KZG opening stay with the caller.
  * d_scalars is a column block d[(c * rows + i) * 4 + limb] in `form` (any B2F_FP_*, reduced: the
  * blocks every other prover call produces); rows >= len are never read. d_bases holds n_bases >=
  * len affine points shared by all columns, a point being (x, y), each coordinate four
@@ -723,6 +723,40 @@ B2F_API int b2f_ipa_fold_dev(b2f_ctx* ctx, uint64_t* d_p, uint64_t* d_b, uint64_
 /* host only: the longest round b2f_ipa_round_dev runs as one direct launch (a power of two) */
 B2F_API uint64_t b2f_ipa_direct_max_len(void);
 
+/* The group NTT: the discrete Fourier transform of n = 2^k curve points over the 2^k domain of the
+ * curve's scalar field. This is what turns the parameters' g into g_lagrange (halo2's
+ * g_to_lagrange in Params::new / ParamsKZG::setup: best_fft over the points with omega^-1, every
+ * point times n^-1, batch-normalised), the bases the Lagrange-form commitments (b2f_msm_cells_dev,
+ * b2f_msm_dev of a Lagrange column) multiply against: g_lagrange = inverse(g). Hash-to-curve for
+ * the IPA's g and the KZG trusted set-up stay with the caller.
+ * d_in holds n points in b2f_msm_dev's layout (64 bytes, base-field Montgomery coordinates, the
+ * identity all zero, not checked to be on the curve: off-curve input gives meaningless points and
+ * never an out-of-range access). `form` only selects the curve: forms 0/1 are Vesta, forms 2/3
+ * BN254 G1. omega is the 2^k domain's generator as canonical limbs of that curve's scalar field, as
+ * for b2f_ntt_columns_dev, in both directions; omega^-1 and n^-1 are derived by the library.
+ *   B2F_NTT_FORWARD  out[i] = sum_j [omega^(i j)] in[j]
+ *   B2F_NTT_INVERSE  out[i] = [n^-1] sum_j [omega^(-i j)] in[j]: the exact inverse of the forward map
+ * d_out receives n affine points in the same layout, the identity as all zeros; the affine form is
+ * canonical, so the result is bit-exact whatever the order of summation. d_out == d_in is allowed
+ * (the transform then runs in place); any other overlap is refused.
+ * Radix-2 stages in place in d_out, the points affine between stages, one launch per stage; the
+ * stage whose twiddle is 1 multiplies nothing and, for the inverse, carries the n multiplications
+ * by n^-1. The n / 2 twiddles are rebuilt on every call in the context's scratch. Asynchronous on
+ * `stream`; pointers are 16-byte aligned; one B2F_KERNEL_QUOTIENT region per call; all byte offsets
+ * are 64-bit. Errors: B2F_ERR_ARG, with nothing launched and the next good call working, for a null
+ * or misaligned pointer, k outside [1, 28], direction > 1, form > 3, omega >= r, or d_in and d_out
+ * overlapping without being equal; B2F_ERR_FIELD at b2f_sync when omega^(2^(k-1)) != -1 (the outputs
+ * are then meaningless; the next call works normally); B2F_ERR_CHECK at b2f_sync if an affine
+ * conversion's inversion fails on a non-identity point (a library defect, as for b2f_msm_dev);
+ * B2F_ERR_HIP for runtime failures, scratch growth included. */
+B2F_API int b2f_group_ntt_dev(b2f_ctx* ctx, const uint64_t* d_in, uint32_t k, const uint64_t omega[4],
+                              uint32_t direction, uint32_t form, uint64_t* d_out, void* stream);
+/* host only: the full-width scalar multiplications the inverse direction performs, n + (n / 2)(k - 1)
+ * (n by n^-1 and n / 2 in each of the k - 1 stages with twiddles, those by the twiddle 1 included; the
+ * forward direction performs the (n / 2)(k - 1) alone), and the scratch bytes of either direction;
+ * B2F_ERR_ARG where the call would refuse k or form. Either output pointer may be null. */
+B2F_API int b2f_group_ntt_plan(uint32_t k, uint32_t form, uint64_t* scalar_muls, uint64_t* scratch_bytes);
+
 /* The advice queries of the chip: the (halo2 advice column, rotation) pairs the sixteen gates read
  * (the list at b2f_quotient_gates_dev), as a set, sorted by column then rotation; writes
  * min(count, cap) pairs (column, rotation) and returns count. These are the evaluations of advice
@@ -748,7 +782,7 @@ B2F_API uint64_t b2f_gate_queries(uint32_t* pairs, uint64_t cap);
 #define B2F_KERNEL_NTT 8    /* NTT of prover columns (table build and all passes of one call) */
 #define B2F_KERNEL_QUOTIENT 9 /* quotient terms, the vanishing divide, the Lagrange selectors and the
                                  evaluation / opening calls; the commitments (b2f_msm_dev, b2f_msm_cells_dev);
-                                 the IPA rounds (b2f_ipa_*_dev) */
+                                 the IPA rounds (b2f_ipa_*_dev); the group NTT (b2f_group_ntt_dev) */
 #define B2F_NUM_KERNELS 10
 /* total_ms and count must each hold b2f_num_kernels() entries (= B2F_NUM_KERNELS of the
  * header the library was built with; it grew from 7 to 8 with B2F_KERNEL_PERM_SIGMA, to 9

@@ -161,6 +161,8 @@ SIGNATURES = [
     ("b2f_ipa_round_dev", I32, [P, P, P, P, U64, ctypes.c_uint32, P, P, P]),
     ("b2f_ipa_fold_dev", I32, [P, P, P, P, U64, P, ctypes.c_uint32, P]),
     ("b2f_ipa_direct_max_len", U64, []),
+    ("b2f_group_ntt_dev", I32, [P, P, ctypes.c_uint32, P, ctypes.c_uint32, ctypes.c_uint32, P, P]),
+    ("b2f_group_ntt_plan", I32, [ctypes.c_uint32, ctypes.c_uint32, P, P]),
     ("b2f_gate_queries", U64, [P, U64]),
     ("b2f_sync", I32, [P, P]),
     ("b2f_fill", I32, [P, P, SIZE, P, P, P]),
@@ -274,6 +276,17 @@ def ipa_direct_max_len(diag=False):
     """Host only (b2f_ipa_direct_max_len): the longest round b2f_ipa_round_dev runs as one direct
     launch. diag=True asks the diagnostics library, which honours B2F_DIAG_IPA_DIRECT=<len>."""
     return int(load(diag=diag).b2f_ipa_direct_max_len())
+
+
+def group_ntt_plan(k, form=FP_MONTGOMERY):
+    """Host only (b2f_group_ntt_plan): the scalar multiplications the inverse group NTT of 2^k
+    points performs and the call's scratch bytes, as a dict. B2FError(ERR_ARG) where the call would
+    refuse k or form."""
+    sm, sb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = load().b2f_group_ntt_plan(int(k), int(form), ctypes.byref(sm), ctypes.byref(sb))
+    if rc != OK:
+        raise B2FError(rc, "no group ntt plan for k = %d, form = %d" % (k, form))
+    return {"scalar_muls": int(sm.value), "scratch_bytes": int(sb.value)}
 
 
 def check(ctx, rc, lib=None):

@@ -659,6 +659,49 @@ class Engine:
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         self.ipa_fold_dev(p.data_ptr(), b.data_ptr(), g.data_ptr(), n, u, form, s)
 
+    # ---------------------------------------------------------------- group NTT (g -> g_lagrange)
+    def group_ntt_dev(self, d_in, k, omega, direction, form, d_out, stream=0):
+        """b2f_group_ntt_dev: the transform of 2^k affine points; omega a Python int (canonical)."""
+        self._check(self.lib.b2f_group_ntt_dev(self.ctx, _vp(d_in), int(k), self._limbs(omega)[0],
+                                               int(direction), int(form), _vp(d_out), _vp(stream)))
+
+    def group_ntt(self, points, k, inverse=False, form=_lib.FP_MONTGOMERY, out=None, stream=None):
+        """The group NTT of the first 2^k rows of `points`, int64 [rows >= 2^k, 8] affine points of
+        the form's curve (curve.pack_points), over the 2^k domain of the form's scalar field
+        (omega from b2f.field.omega): forward, or inverse (with the n^-1). Returns int64 [2^k, 8]
+        affine points, the identity all zeros; out=points transforms in place (rows past 2^k
+        untouched) -- see b2f_group_ntt_dev. Both tensors must be on this engine's GPU.
+        _lib.group_ntt_plan counts the inverse's scalar multiplications, n + (n / 2)(k - 1); the
+        forward direction performs n fewer."""
+        import torch
+
+        from . import field
+
+        n = 1 << int(k)
+        if points.dim() != 2 or points.shape[1] != 8 or points.dtype != torch.int64 or not points.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "group_ntt: points must be contiguous int64 [rows, 8]")
+        if int(points.shape[0]) < n:
+            raise _lib.B2FError(_lib.ERR_ROWS, "group_ntt: points holds fewer than 2^k = %d rows" % n)
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.int64, device=points.device)
+        if out.dim() != 2 or out.shape[1] != 8 or out.dtype != torch.int64 or not out.is_contiguous() \
+                or int(out.shape[0]) < n:
+            raise _lib.B2FError(_lib.ERR_ARG, "group_ntt: out must be contiguous int64 [rows >= 2^k, 8]")
+        for what, t in (("points", points), ("out", out)):
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise _lib.B2FError(_lib.ERR_ARG, "group_ntt: %s is on %s, not on cuda:%d"
+                                    % (what, t.device, self.device))
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.group_ntt_dev(points.data_ptr(), k, field.omega(field.of_form(form), int(k)),
+                           _lib.NTT_INVERSE if inverse else _lib.NTT_FORWARD, form, out.data_ptr(), s)
+        return out
+
+    def g_to_lagrange(self, g, k, form=_lib.FP_MONTGOMERY, out=None, stream=None):
+        """halo2's g_to_lagrange: the Lagrange-basis points of the parameters' g over the 2^k
+        domain, the bases of commit_lagrange (msm_cells, DeviceBatch.commit_advice): the inverse
+        group NTT."""
+        return self.group_ntt(g, k, inverse=True, form=form, out=out, stream=stream)
+
     def debug_curve_op(self, op, a, b, curve, za=None, zb=None):
         """Diagnostics build only (b2f_debug_curve_op): the base-field primitive or point operation
         `op` (a name of _lib.CURVE_OPS) on the device, one lane per element. Field ops: a, b uint64

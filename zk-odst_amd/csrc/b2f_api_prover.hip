@@ -1072,6 +1072,47 @@ B2F_API int b2f_ipa_fold_dev(b2f_ctx* ctx, uint64_t* d_p, uint64_t* d_b, uint64_
   return B2F_OK;
 }
 
+B2F_API int b2f_group_ntt_plan(uint32_t k, uint32_t form, uint64_t* scalar_muls, uint64_t* scratch_bytes) {
+  if (k < 1 || k > 28 || form > B2F_FP_BN254_MONTGOMERY) return B2F_ERR_ARG;
+  if (scalar_muls) *scalar_muls = group_ntt_scalar_muls(k);
+  if (scratch_bytes) *scratch_bytes = group_ntt_scratch_bytes(k);
+  return B2F_OK;
+}
+
+B2F_API int b2f_group_ntt_dev(b2f_ctx* ctx, const uint64_t* d_in, uint32_t k, const uint64_t omega[4],
+                              uint32_t direction, uint32_t form, uint64_t* d_out, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "group ntt";
+  if (!d_in || !d_out || !omega) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (((uintptr_t)d_in | (uintptr_t)d_out) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "%s: buffers must be 16-byte aligned", what);
+  if (k < 1 || k > 28) return set_err(ctx, B2F_ERR_ARG, "%s: k %u not in [1, 28]", what, k);
+  if (direction > B2F_NTT_INVERSE) return set_err(ctx, B2F_ERR_ARG, "%s: unknown direction %u", what, direction);
+  if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "%s: unknown form %u", what, form);
+  if (!fe_canonical(form, omega)) return set_err(ctx, B2F_ERR_ARG, "%s: omega is >= r", what);
+  if (d_in != d_out && ranges_overlap(d_in, 64ull << k, d_out, 64ull << k))
+    return set_err(ctx, B2F_ERR_ARG, "%s: input and output overlap without being equal", what);
+  // omega^-1 and n^-1 for the inverse. A zero omega has no inverse and is no root of unity: the
+  // device's root check reports it, the twiddles are then all zero and the output meaningless.
+  uint64_t tw_base[4], ninv[4];
+  memcpy(tw_base, omega, 32);
+  if (direction == B2F_NTT_INVERSE) {
+    const uint64_t n[4] = {1ull << k, 0, 0, 0};
+    if (!host_inverse(form, n, ninv)) return set_err(ctx, B2F_ERR_CHECK, "%s: the host inversion of n failed", what);
+    if (fe_is_zero(omega)) memset(tw_base, 0, 32);
+    else if (!host_inverse(form, omega, tw_base))
+      return set_err(ctx, B2F_ERR_CHECK, "%s: the host inversion of omega failed", what);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = grow_device(ctx, &ctx->d_gntt, &ctx->gntt_cap, group_ntt_scratch_bytes(k), 1, s)) return rc;
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_group_ntt(d_in, k, omega, tw_base, direction == B2F_NTT_INVERSE ? ninv : nullptr, form, d_out,
+                               ctx->d_gntt, ctx->d_status + 2, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
 B2F_API uint64_t b2f_gate_queries(uint32_t* pairs, uint64_t cap) { return gate_queries(pairs, cap); }
 
 B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_rows,

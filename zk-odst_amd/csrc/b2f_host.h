@@ -97,6 +97,8 @@ struct b2f_ctx {
   bool cells_ev_live;
   void* d_ipa;  // IPA round scratch beyond the commitments' (b2f_ipa.hip: ipa_scratch_bytes)
   size_t ipa_cap;
+  void* d_gntt;  // the group NTT's twiddles (b2f_group_ntt.hip: group_ntt_scratch_bytes)
+  size_t gntt_cap;
 };
 
 namespace b2f {

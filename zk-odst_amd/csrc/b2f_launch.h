@@ -165,6 +165,16 @@ hipError_t launch_ipa_fold(uint64_t* d_p, uint64_t* d_b, uint64_t* d_g, uint64_t
 int diag_ipa_direct(uint64_t* len);
 #endif
 
+// b2f_group_ntt.hip: the group NTT of 2^k affine points, in place in d_out after a bit-reversing
+// copy (or swap, d_out == d_in). omega: the domain's generator (checked on the device); tw_base:
+// omega or, for the inverse, omega^-1; ninv: n^-1 for the inverse, nullptr for the forward
+// direction; all canonical host limbs. scratch holds group_ntt_scratch_bytes(k): the twiddles.
+uint64_t group_ntt_scalar_muls(uint32_t k);
+size_t group_ntt_scratch_bytes(uint32_t k);
+hipError_t launch_group_ntt(const uint64_t* d_in, uint32_t k, const uint64_t* omega, const uint64_t* tw_base,
+                            const uint64_t* ninv, uint32_t form, uint64_t* d_out, void* scratch, int* sticky,
+                            hipStream_t s);
+
 // b2f_export.hip
 hipError_t launch_export_fp(const uint32_t* d_advice, uint64_t total_rows, uint64_t row_begin,
                             uint64_t nrows, uint32_t form, uint64_t* d_out, uint64_t out_rows,
