@@ -728,7 +728,8 @@ B2F_API uint64_t b2f_ipa_direct_max_len(void);
  * g_to_lagrange in Params::new / ParamsKZG::setup: best_fft over the points with omega^-1, every
  * point times n^-1, batch-normalised), the bases the Lagrange-form commitments (b2f_msm_cells_dev,
  * b2f_msm_dev of a Lagrange column) multiply against: g_lagrange = inverse(g). Hash-to-curve for
- * the IPA's g and the KZG trusted set-up stay with the caller.
+ * the IPA's g and a KZG ceremony's points stay with the caller (b2f_fixed_base_mul_dev builds g for
+ * a caller who knows tau).
  * d_in holds n points in b2f_msm_dev's layout (64 bytes, base-field Montgomery coordinates, the
  * identity all zero, not checked to be on the curve: off-curve input gives meaningless points and
  * never an out-of-range access). `form` only selects the curve: forms 0/1 are Vesta, forms 2/3
@@ -757,6 +758,41 @@ B2F_API int b2f_group_ntt_dev(b2f_ctx* ctx, const uint64_t* d_in, uint32_t k, co
  * B2F_ERR_ARG where the call would refuse k or form. Either output pointer may be null. */
 B2F_API int b2f_group_ntt_plan(uint32_t k, uint32_t form, uint64_t* scalar_muls, uint64_t* scratch_bytes);
 
+/* Batched fixed-base scalar multiplication: len multiples of one point. With s_i = tau^i
+ * (b2f_ipa_powers_dev) and B the curve's generator this is g of halo2's ParamsKZG::setup(k, rng),
+ * g[i] = [tau^i] G, whose g_lagrange b2f_group_ntt_dev then derives: the UNSAFE set-up, for a caller
+ * who knows tau (tests, benches, development). A production prover loads a ceremony's points;
+ * [tau] G2, the pairing and hash-to-curve for the IPA's g stay with the caller.
+ * h_base is a HOST affine point in b2f_msm_dev's layout (64 bytes, base-field Montgomery
+ * coordinates, all zero for the identity), read before the call returns. It is NOT checked to be on
+ * the curve: an off-curve base gives meaningless points and never an out-of-range access. `form`
+ * selects the curve and the scalars' form as for b2f_msm_dev: forms 0/1 are Vesta, forms 2/3 BN254
+ * G1, Montgomery scalars are converted at load. d_scalars holds len reduced scalars d[i * 4 + limb]
+ * (what b2f_ipa_powers_dev writes). d_out receives len affine points in the same layout, the identity
+ * as all zeros; the affine form is canonical, so the result is bit-exact. Scalar 0 gives the
+ * identity; the identity base gives all identities.
+ * A scalar is recoded to `windows` signed digits of `window_bits` bits and the output is the sum of
+ * one table entry per non-zero digit (mixed additions, then one inversion per output). The table,
+ * [j 2^(w window_bits)] B for every window w and 1 <= j <= 2^(window_bits - 1), table_points affine
+ * points, is built on the device in the context's scratch on the first call with a base and cached
+ * per (curve, base): four entries, replaced round-robin, the key compared on the host, so a repeated
+ * call with the same base builds nothing. Asynchronous on `stream`; pointers are 16-byte aligned; one
+ * B2F_KERNEL_QUOTIENT region per call (the table build, when there is one, inside it); all byte
+ * offsets are 64-bit. Errors: B2F_ERR_ARG, with nothing launched and the next good call working, for
+ * a null or misaligned pointer, form > 3, len == 0 or len > 2^28, or d_out overlapping d_scalars;
+ * B2F_ERR_CHECK at b2f_sync if an affine conversion's inversion fails on a non-identity point (a
+ * library defect for an on-curve base, as for b2f_msm_dev); B2F_ERR_HIP for runtime failures,
+ * scratch growth included. */
+/* out[i] = [s_i] B, i < len */
+B2F_API int b2f_fixed_base_mul_dev(b2f_ctx* ctx, const uint64_t h_base[8], const uint64_t* d_scalars,
+                                   uint64_t len, uint32_t form, uint64_t* d_out, void* stream);
+/* host only: the digit width, the digits of a scalar, the table's points (windows *
+ * 2^(window_bits - 1): signed digits store half of them) and the scratch bytes of one cached table;
+ * B2F_ERR_ARG, nothing written, where the call would refuse len or form. Any output pointer may be
+ * null. */
+B2F_API int b2f_fixed_base_plan(uint64_t len, uint32_t form, uint32_t* window_bits, uint32_t* windows,
+                                uint64_t* table_points, uint64_t* scratch_bytes);
+
 /* The advice queries of the chip: the (halo2 advice column, rotation) pairs the sixteen gates read
  * (the list at b2f_quotient_gates_dev), as a set, sorted by column then rotation; writes
  * min(count, cap) pairs (column, rotation) and returns count. These are the evaluations of advice
@@ -782,7 +818,8 @@ B2F_API uint64_t b2f_gate_queries(uint32_t* pairs, uint64_t cap);
 #define B2F_KERNEL_NTT 8    /* NTT of prover columns (table build and all passes of one call) */
 #define B2F_KERNEL_QUOTIENT 9 /* quotient terms, the vanishing divide, the Lagrange selectors and the
                                  evaluation / opening calls; the commitments (b2f_msm_dev, b2f_msm_cells_dev);
-                                 the IPA rounds (b2f_ipa_*_dev); the group NTT (b2f_group_ntt_dev) */
+                                 the IPA rounds (b2f_ipa_*_dev); the group NTT (b2f_group_ntt_dev); the
+                                 fixed-base multiples (b2f_fixed_base_mul_dev) */
 #define B2F_NUM_KERNELS 10
 /* total_ms and count must each hold b2f_num_kernels() entries (= B2F_NUM_KERNELS of the
  * header the library was built with; it grew from 7 to 8 with B2F_KERNEL_PERM_SIGMA, to 9

@@ -163,6 +163,8 @@ SIGNATURES = [
     ("b2f_ipa_direct_max_len", U64, []),
     ("b2f_group_ntt_dev", I32, [P, P, ctypes.c_uint32, P, ctypes.c_uint32, ctypes.c_uint32, P, P]),
     ("b2f_group_ntt_plan", I32, [ctypes.c_uint32, ctypes.c_uint32, P, P]),
+    ("b2f_fixed_base_mul_dev", I32, [P, P, P, U64, ctypes.c_uint32, P, P]),
+    ("b2f_fixed_base_plan", I32, [U64, ctypes.c_uint32, P, P, P, P]),
     ("b2f_gate_queries", U64, [P, U64]),
     ("b2f_sync", I32, [P, P]),
     ("b2f_fill", I32, [P, P, SIZE, P, P, P]),
@@ -287,6 +289,20 @@ def group_ntt_plan(k, form=FP_MONTGOMERY):
     if rc != OK:
         raise B2FError(rc, "no group ntt plan for k = %d, form = %d" % (k, form))
     return {"scalar_muls": int(sm.value), "scratch_bytes": int(sb.value)}
+
+
+def fixed_base_plan(len_, form=FP_MONTGOMERY):
+    """Host only (b2f_fixed_base_plan): the signed-digit width, the digits of a scalar, the points
+    of one base's table (windows * 2^(window_bits - 1)) and its bytes, as a dict.
+    B2FError(ERR_ARG) where the call would refuse len or form."""
+    c, w = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    tp, sb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = load().b2f_fixed_base_plan(int(len_), int(form), ctypes.byref(c), ctypes.byref(w), ctypes.byref(tp),
+                                    ctypes.byref(sb))
+    if rc != OK:
+        raise B2FError(rc, "no fixed base plan for len = %d, form = %d" % (len_, form))
+    return {"window_bits": int(c.value), "windows": int(w.value), "table_points": int(tp.value),
+            "scratch_bytes": int(sb.value)}
 
 
 def check(ctx, rc, lib=None):

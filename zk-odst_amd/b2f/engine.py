@@ -702,6 +702,64 @@ class Engine:
         group NTT."""
         return self.group_ntt(g, k, inverse=True, form=form, out=out, stream=stream)
 
+    # ---------------------------------------------------------------- fixed-base multiples, KZG set-up
+    def fixed_base_mul_dev(self, base, d_scalars, len_, form, d_out, stream=0):
+        """b2f_fixed_base_mul_dev: d_out[i] = [s_i] B. base: the packed host point, 8 uint64 limbs
+        (curve.pack_points; all zero: the identity)."""
+        limbs = np.ascontiguousarray(base, dtype=np.uint64).reshape(-1)
+        if limbs.size != 8:
+            raise _lib.B2FError(_lib.ERR_ARG, "fixed_base_mul: the base is 8 limbs")
+        self._check(self.lib.b2f_fixed_base_mul_dev(self.ctx, _np_ptr(limbs), _vp(d_scalars), int(len_),
+                                                    int(form), _vp(d_out), _vp(stream)))
+
+    def fixed_base_mul(self, scalars, base=None, form=_lib.FP_MONTGOMERY, out=None, stream=None):
+        """Multiples of one point (b2f_fixed_base_mul_dev): out[i] = [scalars[i]] B. scalars: int64
+        [len, 4] reduced scalars in `form`; base: None for the generator of the form's curve
+        (curve.GENERATOR), an (x, y) pair of Python ints, or 8 packed limbs (curve.pack_points: the
+        identity all zeros). Returns int64 [len, 8] affine points, the identity all zeros. The
+        base's table is built on the first call with it and cached by the engine's context (four
+        bases); _lib.fixed_base_plan reports its shape."""
+        import torch
+
+        from . import curve
+
+        if scalars.dim() != 2 or scalars.shape[1] != 4 or scalars.dtype != torch.int64 or not scalars.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "fixed_base_mul: scalars must be contiguous int64 [len, 4]")
+        n = int(scalars.shape[0])
+        cv = curve.of_form(form)
+        if base is None:
+            base = curve.GENERATOR[cv]
+        if isinstance(base, tuple) and builtins.len(base) == 2:
+            base = curve.pack_points(cv, [base])[0]
+        if out is None:
+            out = torch.empty((n, 8), dtype=torch.int64, device=scalars.device)
+        if out.dim() != 2 or out.shape[1] != 8 or out.dtype != torch.int64 or not out.is_contiguous() \
+                or int(out.shape[0]) < n:
+            raise _lib.B2FError(_lib.ERR_ARG, "fixed_base_mul: out must be contiguous int64 [rows >= len, 8]")
+        for what, t in (("scalars", scalars), ("out", out)):
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise _lib.B2FError(_lib.ERR_ARG, "fixed_base_mul: %s is on %s, not on cuda:%d"
+                                    % (what, t.device, self.device))
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.fixed_base_mul_dev(base, scalars.data_ptr(), n, form, out.data_ptr(), s)
+        return out
+
+    def kzg_setup(self, k, tau, form=_lib.FP_BN254_MONTGOMERY, lagrange=True, stream=None):
+        """halo2's UNSAFE KZG set-up, ParamsKZG::setup(k, rng) with the caller's tau in the place
+        of the rng's: g[i] = [tau^i] G for i < 2^k (G: curve.GENERATOR of the form's curve) and
+        g_lagrange = g_to_lagrange(g). Returns (g, g_lagrange), int64 [2^k, 8] each (g_lagrange is
+        None with lagrange=False). It composes ipa_powers(tau, 2^k), fixed_base_mul and
+        g_to_lagrange on `stream`.
+
+        tau is known to the caller, so whoever holds it can forge openings: this is for tests,
+        benches and development, exactly as ParamsKZG::setup is. A production caller loads the
+        points of a ceremony instead and never calls this. [tau] G2 and the pairing are not built
+        here."""
+        n = 1 << int(k)
+        powers = self.ipa_powers(int(tau), n, form=form, stream=stream)
+        g = self.fixed_base_mul(powers, form=form, stream=stream)
+        return g, (self.g_to_lagrange(g, k, form=form, stream=stream) if lagrange else None)
+
     def debug_curve_op(self, op, a, b, curve, za=None, zb=None):
         """Diagnostics build only (b2f_debug_curve_op): the base-field primitive or point operation
         `op` (a name of _lib.CURVE_OPS) on the device, one lane per element. Field ops: a, b uint64

@@ -1113,6 +1113,52 @@ B2F_API int b2f_group_ntt_dev(b2f_ctx* ctx, const uint64_t* d_in, uint32_t k, co
   return B2F_OK;
 }
 
+B2F_API int b2f_fixed_base_plan(uint64_t len, uint32_t form, uint32_t* window_bits, uint32_t* windows,
+                                uint64_t* table_points, uint64_t* scratch_bytes) {
+  if (len == 0 || len > (1ull << 28) || form > B2F_FP_BN254_MONTGOMERY) return B2F_ERR_ARG;
+  fixed_base_plan_of(window_bits, windows, table_points, scratch_bytes);
+  return B2F_OK;
+}
+
+B2F_API int b2f_fixed_base_mul_dev(b2f_ctx* ctx, const uint64_t h_base[8], const uint64_t* d_scalars, uint64_t len,
+                                   uint32_t form, uint64_t* d_out, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "fixed base mul";
+  if (!h_base || !d_scalars || !d_out) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (((uintptr_t)d_scalars | (uintptr_t)d_out) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "%s: buffers must be 16-byte aligned", what);
+  if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "%s: unknown form %u", what, form);
+  if (len == 0 || len > (1ull << 28))
+    return set_err(ctx, B2F_ERR_ARG, "%s: len %llu not in [1, 2^28]", what, (unsigned long long)len);
+  if (ranges_overlap(d_out, 64 * len, d_scalars, 32 * len))
+    return set_err(ctx, B2F_ERR_ARG, "%s: the output overlaps the scalars", what);
+  uint64_t table_bytes = 0;
+  fixed_base_plan_of(nullptr, nullptr, nullptr, &table_bytes);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // the table of this (curve, base): cached, or built into the next slot
+  b2f_fixed_base_tab* tab = nullptr;
+  for (auto& t : ctx->fb_tab)
+    if (t.live && t.curve == (form >> 1) && !memcmp(t.base, h_base, 64)) tab = &t;
+  int tk = -1;
+  if (!tab) {
+    b2f_fixed_base_tab& t = ctx->fb_tab[ctx->fb_next++ % b2f_ctx::FB_TABS];
+    t.live = false;
+    if (int rc = grow_device(ctx, &t.d, &t.cap, table_bytes, 1, s)) return rc;
+    t.curve = form >> 1;
+    memcpy(t.base, h_base, 64);
+    tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+    HIPCHK(ctx, launch_fixed_base_table(h_base, form, (uint64_t*)t.d, ctx->d_status + 2, s));
+    t.live = true;
+    tab = &t;
+  } else {
+    tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  }
+  HIPCHK(ctx, launch_fixed_base_mul(d_scalars, len, form, (const uint64_t*)tab->d, d_out, ctx->d_status + 2, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
 B2F_API uint64_t b2f_gate_queries(uint32_t* pairs, uint64_t cap) { return gate_queries(pairs, cap); }
 
 B2F_API int b2f_ntt_columns_dev(b2f_ctx* ctx, const uint64_t* d_in, uint64_t in_rows,

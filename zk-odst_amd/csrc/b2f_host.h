@@ -23,6 +23,16 @@ struct b2f_domain_tab {
   bool live;  // set once the launch that fills the block was issued without error
 };
 
+// The table of one fixed base (b2f_fixed_base_mul_dev), cached by (curve, base) and replaced
+// round-robin like the domain tables; the key is compared on the host.
+struct b2f_fixed_base_tab {
+  uint32_t curve;
+  uint64_t base[8];
+  void* d;
+  size_t cap;
+  bool live;
+};
+
 struct b2f_ctx {
   int device;
   char err[512];
@@ -99,6 +109,9 @@ struct b2f_ctx {
   size_t ipa_cap;
   void* d_gntt;  // the group NTT's twiddles (b2f_group_ntt.hip: group_ntt_scratch_bytes)
   size_t gntt_cap;
+  static constexpr int FB_TABS = 4;
+  b2f_fixed_base_tab fb_tab[FB_TABS];  // b2f_fixed_base.hip
+  uint32_t fb_next;
 };
 
 namespace b2f {

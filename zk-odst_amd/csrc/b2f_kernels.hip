@@ -1171,6 +1171,7 @@ B2F_API void b2f_destroy(b2f_ctx* ctx) {
   (void)hipFree(ctx->d_msm);
   (void)hipFree(ctx->d_ipa);
   (void)hipFree(ctx->d_gntt);
+  for (auto& t : ctx->fb_tab) (void)hipFree(t.d);
   if (ctx->op_ev_live) (void)hipEventSynchronize(ctx->op_ev);
   if (ctx->op_ev) (void)hipEventDestroy(ctx->op_ev);
   (void)hipHostFree(ctx->h_op);

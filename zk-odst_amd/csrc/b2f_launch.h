@@ -175,6 +175,16 @@ hipError_t launch_group_ntt(const uint64_t* d_in, uint32_t k, const uint64_t* om
                             const uint64_t* ninv, uint32_t form, uint64_t* d_out, void* scratch, int* sticky,
                             hipStream_t s);
 
+// b2f_fixed_base.hip: out[i] = [s_i] B. The plan is constant: the window bits, the windows of a
+// scalar, the table's points (windows * 2^(bits - 1), signed digits) and its bytes. The table
+// launch fills d_table from the host affine point `base` (8 limbs, base-field Montgomery form); the
+// multiplication reads it. Both raise B2F_ERR_CHECK in sticky when an affine conversion fails.
+void fixed_base_plan_of(uint32_t* window_bits, uint32_t* windows, uint64_t* table_points, uint64_t* table_bytes);
+hipError_t launch_fixed_base_table(const uint64_t* base, uint32_t form, uint64_t* d_table, int* sticky,
+                                   hipStream_t s);
+hipError_t launch_fixed_base_mul(const uint64_t* d_scalars, uint64_t len, uint32_t form, const uint64_t* d_table,
+                                 uint64_t* d_out, int* sticky, hipStream_t s);
+
 // b2f_export.hip
 hipError_t launch_export_fp(const uint32_t* d_advice, uint64_t total_rows, uint64_t row_begin,
                             uint64_t nrows, uint32_t form, uint64_t* d_out, uint64_t out_rows,
