@@ -602,8 +602,8 @@ B2F_API int b2f_kate_divide_dev(b2f_ctx* ctx, const uint64_t* d_cols, uint64_t r
  * field `form` names: Vesta (y^2 = x^3 + 5 over pasta Fq, group order pasta Fp) for forms 0/1,
  * BN254 G1 (y^2 = x^3 + 3 over bn256::Fq, group order bn256::Fr) for forms 2/3. This is halo2's
  * commit / commit_lagrange of a column against the parameters' points (g, g_lagrange);
- * b2f_group_ntt_dev derives g_lagrange from g; choosing g, the blinding term's generator, the
- * transcript and the IPA / KZG opening stay with the caller.
+ * b2f_group_ntt_dev derives g_lagrange from g; choosing g and the blinding term's generator stay
+ * with the caller (the transcript: b2f_transcript_*_dev; the IPA opening: b2f_ipa_open_dev).
  * d_scalars is a column block d[(c * rows + i) * 4 + limb] in `form` (any B2F_FP_*, reduced: the
  * blocks every other prover call produces); rows >= len are never read. d_bases holds n_bases >=
  * len affine points shared by all columns, a point being (x, y), each coordinate four
@@ -697,8 +697,9 @@ B2F_API uint32_t b2f_fixed_cell_columns(uint64_t total_rows, uint64_t row_begin,
  *   value_l = <p[half..], b[..half]>   value_r = <p[..half], b[half..]>
  *   caller: L += [value_l z] U + [l_rand] W, the same for R; writes both; squeezes u
  *   p[i] += p[half+i] u^-1   b[i] += b[half+i] u   G[i] = affine(G[i] + [u] G[half+i])   (b2f_ipa_fold_dev)
- * and after log2(len) rounds c = p[0]. The transcript, the blinding scalars, the s_poly masking and
- * the U / W terms stay with the caller; every challenge is a host argument (canonical limbs).
+ * and after log2(len) rounds c = p[0]. For these three calls the transcript, the blinding scalars
+ * and the U / W terms stay with the caller and every challenge is a host argument (canonical limbs);
+ * b2f_ipa_open_dev below queues the whole loop, caller's lines included, on a device transcript.
  * All three calls are asynchronous on `stream`, take 16-byte aligned pointers, use the context's
  * scratch and are one B2F_KERNEL_QUOTIENT region each. Errors, nothing launched and the next good
  * call works: B2F_ERR_ARG for a null or misaligned pointer, form > 3, a len that is not a power of
@@ -722,6 +723,75 @@ B2F_API int b2f_ipa_fold_dev(b2f_ctx* ctx, uint64_t* d_p, uint64_t* d_b, uint64_
                              const uint64_t h_u[4], uint32_t form, void* stream);
 /* host only: the longest round b2f_ipa_round_dev runs as one direct launch (a power of two) */
 B2F_API uint64_t b2f_ipa_direct_max_len(void);
+
+/* The Fiat-Shamir transcript on the device: halo2's Blake2bWrite with Challenge255 (halo2_proofs
+ * 0.3.0 transcript.rs), so that a challenge can stay where the previous call left it. The hash is
+ * BLAKE2b with a 64-byte digest, no key and the personalisation "Halo2-Transcript".
+ *   common_point(P)    absorbs the byte 1, then x and y of the affine point as 32 little-endian
+ *                      bytes each, canonical (write_point hashes the same bytes)
+ *   common_scalar(s)   absorbs the byte 2, then 32 little-endian bytes of the canonical scalar
+ *   squeeze_challenge  absorbs the byte 0 into the running state, finalises a COPY of it, reads the
+ *                      64 digest bytes as a 512-bit little-endian integer and reduces it modulo
+ *                      the scalar field's r (from_uniform_bytes); the running state goes on
+ * The state is B2F_TRANSCRIPT_BYTES of device memory, 16-byte aligned, and its layout is part of
+ * this ABI, so a host with a BLAKE2b of its own can export a transcript it began or import one the
+ * device moved on. As uint64_t words:
+ *   0..7    h (after init: the IV xor the parameter block 0x01010040 and the personalisation)
+ *   8..9    t, the bytes compressed so far, low word first (a multiple of 128)
+ *   10..25  the 128-byte block buffer; bytes at and past the count are zero in every state these
+ *           calls write (an imported state need not keep that)
+ *   26      the bytes in the buffer, 0..128 (a larger value is read as 128)
+ *   27..31  zero
+ * A full buffer is compressed only when the next byte arrives: BLAKE2's lazy last block, whose
+ * compression carries the final flag. So the bytes absorbed so far are t + word 26.
+ * d_points holds n affine points in b2f_msm_dev's layout (64 bytes, base-field Montgomery
+ * coordinates), absorbed in order; `form` selects the curve (0/1 Vesta, 2/3 BN254 G1). The
+ * identity (all zero), which halo2 refuses to write, absorbs the byte 1 and 64 zero bytes, so the
+ * state stays defined, and reports B2F_ERR_FIELD at b2f_sync. d_scalars holds d[i * 4 + limb] in
+ * `form`, reduced. d_challenge receives four canonical limbs of the form's scalar field whatever
+ * the form: how every challenge is passed in this ABI (and what b2f_ipa_open_dev's d_z takes).
+ * One workgroup: its lanes convert a chunk of 256 elements to bytes in LDS, one lane hashes.
+ * Asynchronous on `stream`; one B2F_KERNEL_QUOTIENT region per call. B2F_ERR_ARG, with nothing
+ * launched and the next good call working: a null or misaligned (16 B) pointer, form > 3, n == 0
+ * or n > 2^20, the state overlapping the data or the challenge. */
+#define B2F_TRANSCRIPT_BYTES 256
+B2F_API int b2f_transcript_init_dev(b2f_ctx* ctx, uint64_t* d_state, void* stream);
+B2F_API int b2f_transcript_absorb_points_dev(b2f_ctx* ctx, uint64_t* d_state, const uint64_t* d_points,
+                                             uint64_t n, uint32_t form, void* stream);
+B2F_API int b2f_transcript_absorb_scalars_dev(b2f_ctx* ctx, uint64_t* d_state, const uint64_t* d_scalars,
+                                              uint64_t n, uint32_t form, void* stream);
+B2F_API int b2f_transcript_squeeze_dev(b2f_ctx* ctx, uint64_t* d_state, uint32_t form,
+                                       uint64_t* d_challenge, void* stream);
+
+/* The whole opening loop in one queued call: with k = log2(len), for j = 0 .. k - 1 on the
+ * current length (len, len / 2, .., 2)
+ *   1  L, R, value_l, value_r as b2f_ipa_round_dev forms them (the same launches)
+ *   2  L_j = L + [value_l z] U + [l_rand_j] W,  R_j = R + [value_r z] U + [r_rand_j] W, affine, to
+ *      d_lr[16 j .. 16 j + 7] and d_lr[16 j + 8 .. 16 j + 15]
+ *   3  L_j then R_j absorbed as points into the transcript at d_state; u_j squeezed to
+ *      d_u[4 j ..], canonical
+ *   4  f += l_rand_j u_j^-1 + r_rand_j u_j, u_j^-1 formed on the device
+ *   5  the three folds of b2f_ipa_fold_dev with u_j and u_j^-1 read from device memory
+ * and then c = p[0]; c, then f, absorbed as scalars (write_scalar twice); d_cf[0..3] = c,
+ * d_cf[4..7] = f, both in `form`. No host step lies between the rounds: the call returns once
+ * everything is queued. d_p, d_b, d_g: as for the three calls above, folded in place. d_z: four
+ * canonical limbs on the device (a squeeze's output). d_rand: 2k scalars in `form`, reduced,
+ * l_rand_0, r_rand_0, l_rand_1, ..: the randomness is the caller's. d_cf[4..7] on entry: the
+ * starting f, in `form`. h_u_point, h_w_point: HOST affine points in b2f_msm_dev's layout, read
+ * before the call returns; their multiples come from the cached tables of
+ * b2f_fixed_base_mul_dev (two entries of its cache, built on the first call with a base), one
+ * table entry per lane summed in LDS, so the blinding adds no doubling chain to a round. Choosing
+ * g, U and W, the s_poly masking before the loop and the byte encoding of the proof stay with the
+ * caller. Errors: B2F_ERR_ARG, nothing launched and the next good call working, for what the three
+ * calls refuse, a null or misaligned pointer, U or W the identity, or any buffer the call writes
+ * (the vectors, the state, d_lr [128 k bytes], d_u [32 k], d_cf [64]) overlapping another buffer
+ * of the call; B2F_ERR_FIELD at b2f_sync if an L_j or R_j is the identity or a u_j is zero (halo2
+ * fails there too; the outputs are then meaningless); B2F_ERR_CHECK and B2F_ERR_HIP as above. One
+ * B2F_KERNEL_QUOTIENT region. */
+B2F_API int b2f_ipa_open_dev(b2f_ctx* ctx, uint64_t* d_p, uint64_t* d_b, uint64_t* d_g, uint64_t len,
+                             const uint64_t h_u_point[8], const uint64_t h_w_point[8],
+                             const uint64_t* d_z, const uint64_t* d_rand, uint64_t* d_state,
+                             uint32_t form, uint64_t* d_lr, uint64_t* d_u, uint64_t* d_cf, void* stream);
 
 /* The group NTT: the discrete Fourier transform of n = 2^k curve points over the 2^k domain of the
  * curve's scalar field. This is what turns the parameters' g into g_lagrange (halo2's
@@ -819,7 +889,8 @@ B2F_API uint64_t b2f_gate_queries(uint32_t* pairs, uint64_t cap);
 #define B2F_KERNEL_QUOTIENT 9 /* quotient terms, the vanishing divide, the Lagrange selectors and the
                                  evaluation / opening calls; the commitments (b2f_msm_dev, b2f_msm_cells_dev);
                                  the IPA rounds (b2f_ipa_*_dev); the group NTT (b2f_group_ntt_dev); the
-                                 fixed-base multiples (b2f_fixed_base_mul_dev) */
+                                 fixed-base multiples (b2f_fixed_base_mul_dev); the transcript
+                                 (b2f_transcript_*_dev) and the one-call opening (b2f_ipa_open_dev) */
 #define B2F_NUM_KERNELS 10
 /* total_ms and count must each hold b2f_num_kernels() entries (= B2F_NUM_KERNELS of the
  * header the library was built with; it grew from 7 to 8 with B2F_KERNEL_PERM_SIGMA, to 9

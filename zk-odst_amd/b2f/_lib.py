@@ -30,6 +30,7 @@ KERNEL_NAMES = ["record", "fill", "eval", "export", "fill_eval", "lookup", "perm
                 "perm_sigma", "ntt", "quotient"]  # B2F_KERNEL_*
 FP_CANONICAL, FP_MONTGOMERY, FP_BN254_CANONICAL, FP_BN254_MONTGOMERY = 0, 1, 2, 3  # B2F_FP_*
 NTT_FORWARD, NTT_INVERSE = 0, 1  # B2F_NTT_*
+TRANSCRIPT_BYTES = 256  # B2F_TRANSCRIPT_BYTES
 FIXED_RESIDENT = 1  # B2F_FIXED_RESIDENT (b2f_fill_eval_dev_ex flags)
 
 OK, ERR_ARG, ERR_ROUNDS, ERR_ROWS, ERR_HIP, ERR_LAYOUT, ERR_INPUT, ERR_FIELD, ERR_CHECK = range(9)
@@ -161,6 +162,11 @@ SIGNATURES = [
     ("b2f_ipa_round_dev", I32, [P, P, P, P, U64, ctypes.c_uint32, P, P, P]),
     ("b2f_ipa_fold_dev", I32, [P, P, P, P, U64, P, ctypes.c_uint32, P]),
     ("b2f_ipa_direct_max_len", U64, []),
+    ("b2f_transcript_init_dev", I32, [P, P, P]),
+    ("b2f_transcript_absorb_points_dev", I32, [P, P, P, U64, ctypes.c_uint32, P]),
+    ("b2f_transcript_absorb_scalars_dev", I32, [P, P, P, U64, ctypes.c_uint32, P]),
+    ("b2f_transcript_squeeze_dev", I32, [P, P, ctypes.c_uint32, P, P]),
+    ("b2f_ipa_open_dev", I32, [P, P, P, P, U64, P, P, P, P, P, ctypes.c_uint32, P, P, P, P]),
     ("b2f_group_ntt_dev", I32, [P, P, ctypes.c_uint32, P, ctypes.c_uint32, ctypes.c_uint32, P, P]),
     ("b2f_group_ntt_plan", I32, [ctypes.c_uint32, ctypes.c_uint32, P, P]),
     ("b2f_fixed_base_mul_dev", I32, [P, P, P, U64, ctypes.c_uint32, P, P]),
@@ -183,6 +189,8 @@ DIAG_SIGNATURES = [
 # op codes of b2f_debug_field_op (csrc/b2f_fieldprobe.hip)
 FIELD_OPS = ["mul", "mul_comba", "mul_cios", "add", "sub", "from_u32", "to_mont", "to_canonical",
              "fe_pow", "inv", "inv_kaliski", "inv_safegcd", "inv_fermat"]
+# apart from those (its operands are any two 256-bit integers, not field elements): (a + b 2^256) mod p
+FIELD_OP_REDUCE_WIDE = 32
 
 # op codes of b2f_debug_curve_op (csrc/b2f_curveprobe.hip): the first CURVE_FIELD_OPS are
 # base-field primitives (four-limb operands), the rest point operations (eight-limb points)

@@ -659,6 +659,136 @@ class Engine:
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         self.ipa_fold_dev(p.data_ptr(), b.data_ptr(), g.data_ptr(), n, u, form, s)
 
+    # ---------------------------------------------------------------- transcript, one-call opening
+    def transcript_init_dev(self, d_state, stream=0):
+        """b2f_transcript_init_dev: the empty transcript into the 32 words at d_state."""
+        self._check(self.lib.b2f_transcript_init_dev(self.ctx, _vp(d_state), _vp(stream)))
+
+    def transcript_absorb_points_dev(self, d_state, d_points, n, form, stream=0):
+        """b2f_transcript_absorb_points_dev: common_point of n affine points, in order."""
+        self._check(self.lib.b2f_transcript_absorb_points_dev(self.ctx, _vp(d_state), _vp(d_points), int(n),
+                                                              int(form), _vp(stream)))
+
+    def transcript_absorb_scalars_dev(self, d_state, d_scalars, n, form, stream=0):
+        """b2f_transcript_absorb_scalars_dev: common_scalar of n scalars in `form`, in order."""
+        self._check(self.lib.b2f_transcript_absorb_scalars_dev(self.ctx, _vp(d_state), _vp(d_scalars), int(n),
+                                                               int(form), _vp(stream)))
+
+    def transcript_squeeze_dev(self, d_state, form, d_challenge, stream=0):
+        """b2f_transcript_squeeze_dev: squeeze_challenge, four canonical limbs to d_challenge."""
+        self._check(self.lib.b2f_transcript_squeeze_dev(self.ctx, _vp(d_state), int(form), _vp(d_challenge),
+                                                        _vp(stream)))
+
+    def ipa_open_dev(self, d_p, d_b, d_g, len_, u_point, w_point, d_z, d_rand, d_state, form, d_lr, d_u, d_cf,
+                     stream=0):
+        """b2f_ipa_open_dev: the whole opening loop queued on `stream`. u_point, w_point: packed host
+        points, 8 uint64 limbs each (curve.pack_points)."""
+        pts = []
+        for base in (u_point, w_point):
+            limbs = np.ascontiguousarray(base, dtype=np.uint64).reshape(-1)
+            if limbs.size != 8:
+                raise _lib.B2FError(_lib.ERR_ARG, "ipa_open: U and W are 8 limbs each")
+            pts.append(limbs)
+        self._check(self.lib.b2f_ipa_open_dev(self.ctx, _vp(d_p), _vp(d_b), _vp(d_g), int(len_), _np_ptr(pts[0]),
+                                              _np_ptr(pts[1]), _vp(d_z), _vp(d_rand), _vp(d_state), int(form),
+                                              _vp(d_lr), _vp(d_u), _vp(d_cf), _vp(stream)))
+
+    @staticmethod
+    def _rows(name, what, t, width, min_rows=1):
+        import torch
+
+        if t.dim() != 2 or t.shape[1] != width or t.dtype != torch.int64 or not t.is_contiguous() \
+                or int(t.shape[0]) < min_rows:
+            raise _lib.B2FError(_lib.ERR_ARG, "%s: %s must be contiguous int64 [rows >= %d, %d]"
+                                % (name, what, min_rows, width))
+
+    @staticmethod
+    def _state(name, state):
+        import torch
+
+        if state.dim() != 1 or state.shape[0] != _lib.TRANSCRIPT_BYTES // 8 or state.dtype != torch.int64 \
+                or not state.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "%s: state must be contiguous int64 [32]" % name)
+
+    def transcript_init(self, stream=None):
+        """A new transcript (b2f_transcript_init_dev): the state, int64 [32] on this engine's GPU, whose
+        words are the ABI of include/b2f.h (h, t, the block buffer, the buffered bytes)."""
+        import torch
+
+        state = torch.empty(_lib.TRANSCRIPT_BYTES // 8, dtype=torch.int64, device="cuda:%d" % self.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.transcript_init_dev(state.data_ptr(), s)
+        return state
+
+    def transcript_absorb_points(self, state, points, form=_lib.FP_MONTGOMERY, stream=None):
+        """common_point of every row of points, int64 [n, 8] affine points of the form's curve
+        (curve.pack_points), in order. An identity row reports B2F_ERR_FIELD at sync."""
+        import torch
+
+        self._state("transcript_absorb_points", state)
+        self._rows("transcript_absorb_points", "points", points, 8)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.transcript_absorb_points_dev(state.data_ptr(), points.data_ptr(), int(points.shape[0]), form, s)
+
+    def transcript_absorb_scalars(self, state, scalars, form=_lib.FP_MONTGOMERY, stream=None):
+        """common_scalar of every row of scalars, int64 [n, 4] in `form`, in order."""
+        import torch
+
+        self._state("transcript_absorb_scalars", state)
+        self._rows("transcript_absorb_scalars", "scalars", scalars, 4)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.transcript_absorb_scalars_dev(state.data_ptr(), scalars.data_ptr(), int(scalars.shape[0]), form, s)
+
+    def transcript_squeeze(self, state, form=_lib.FP_MONTGOMERY, out=None, stream=None):
+        """squeeze_challenge: int64 [4], the canonical limbs of a challenge of the form's scalar field
+        (whatever the form), on the device: what ipa_open takes as z."""
+        import torch
+
+        self._state("transcript_squeeze", state)
+        if out is None:
+            out = torch.empty(4, dtype=torch.int64, device=state.device)
+        if out.dim() != 1 or out.shape[0] != 4 or out.dtype != torch.int64 or not out.is_contiguous():
+            raise _lib.B2FError(_lib.ERR_ARG, "transcript_squeeze: out must be contiguous int64 [4]")
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        self.transcript_squeeze_dev(state.data_ptr(), form, out.data_ptr(), s)
+        return out
+
+    def ipa_open(self, p, b, g, U, W, z, rand, state, f, len=None, form=_lib.FP_MONTGOMERY, stream=None):
+        """The whole opening in one queued call (b2f_ipa_open_dev): every round's blinded L_j, R_j,
+        the challenges u_j squeezed from `state` on the device, the folds, c and f, with no host step
+        between rounds. p, b, g: as for ipa_round, folded in place; U, W: (x, y) pairs of Python ints
+        or 8 packed limbs; z: int64 [4] canonical limbs on the device (transcript_squeeze); rand:
+        int64 [2 k, 4] in `form`, (l_rand_j, r_rand_j) per round; f: int64 [4], the starting f in
+        `form`. Returns (lr int64 [k, 2, 8], u int64 [k, 4] canonical, cf int64 [2, 4] = (c, f) in
+        `form`)."""
+        import torch
+
+        from . import curve
+
+        n = int(p.shape[0]) if len is None else int(len)
+        self._ipa_vectors("ipa_open", p, b, g, n)
+        k = max(n.bit_length() - 1, 1)
+        self._state("ipa_open", state)
+        self._rows("ipa_open", "rand", rand, 4, 2 * k)
+        for what, t in (("z", z), ("f", f)):
+            if t.dim() != 1 or t.shape[0] != 4 or t.dtype != torch.int64 or not t.is_contiguous():
+                raise _lib.B2FError(_lib.ERR_ARG, "ipa_open: %s must be contiguous int64 [4]" % what)
+        cv = curve.of_form(form)
+        U, W = [curve.pack_points(cv, [pt])[0] if isinstance(pt, tuple) and builtins.len(pt) == 2 else pt
+                for pt in (U, W)]
+        lr = torch.empty((k, 2, 8), dtype=torch.int64, device=p.device)
+        u = torch.empty((k, 4), dtype=torch.int64, device=p.device)
+        cf = torch.empty((2, 4), dtype=torch.int64, device=p.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        if s == torch.cuda.current_stream().cuda_stream:
+            cf[1].copy_(f)  # the starting f, ordered on the call's stream
+        else:
+            with torch.cuda.stream(torch.cuda.ExternalStream(s)):
+                cf[1].copy_(f)
+        self.ipa_open_dev(p.data_ptr(), b.data_ptr(), g.data_ptr(), n, U, W, z.data_ptr(), rand.data_ptr(),
+                          state.data_ptr(), form, lr.data_ptr(), u.data_ptr(), cf.data_ptr(), s)
+        return lr, u, cf
+
     # ---------------------------------------------------------------- group NTT (g -> g_lagrange)
     def group_ntt_dev(self, d_in, k, omega, direction, form, d_out, stream=0):
         """b2f_group_ntt_dev: the transform of 2^k affine points; omega a Python int (canonical)."""
@@ -817,6 +947,22 @@ class Engine:
         if rc != _lib.OK:
             raise _lib.B2FError(rc, "debug_field_op(%s) refused or failed" % op)
         return out, flags
+
+    def debug_reduce_wide(self, a, b, field):
+        """Diagnostics build only (b2f_debug_field_op, op FIELD_OP_REDUCE_WIDE): (a + b 2^256) mod p on
+        the device, canonical, one lane per pair. a, b: uint64 [n, 4] host limbs, ANY 256-bit integers
+        (the two halves of a 64-byte digest); field: 0 pallas, 1 BN254. Returns out uint64 [n, 4]."""
+        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
+        b = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 4)
+        if len(a) != len(b):
+            raise _lib.B2FError(_lib.ERR_ARG, "debug_reduce_wide: a and b differ in length")
+        out = np.zeros_like(a)
+        flags = np.zeros(len(a), dtype=np.uint32)
+        rc = self.lib.b2f_debug_field_op(int(field), _lib.FIELD_OP_REDUCE_WIDE, _np_ptr(a), _np_ptr(b),
+                                         len(a), _np_ptr(out), _np_ptr(flags))
+        if rc != _lib.OK:
+            raise _lib.B2FError(rc, "debug_reduce_wide refused or failed")
+        return out
 
     def sync(self, stream=0):
         self._check(self.lib.b2f_sync(self.ctx, _vp(stream)))

@@ -1072,6 +1072,185 @@ B2F_API int b2f_ipa_fold_dev(b2f_ctx* ctx, uint64_t* d_p, uint64_t* d_b, uint64_
   return B2F_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// The cached table of a fixed base (b2f_fixed_base_mul_dev, and U and W of b2f_ipa_open_dev): the
+// live entry of this (curve, base), or the next slot round-robin claimed for it (never `keep`, the
+// other base's entry of the same call). *build: the slot's table is still to be launched (the
+// caller does it inside its timed region and then sets live).
+int fixed_base_table_slot(b2f_ctx* ctx, const uint64_t* h_base, uint32_t form, const b2f_fixed_base_tab* keep,
+                   hipStream_t s, b2f_fixed_base_tab** tab, bool* build) {
+  *build = false;
+  for (auto& t : ctx->fb_tab)
+    if (t.live && t.curve == (form >> 1) && !memcmp(t.base, h_base, 64)) {
+      *tab = &t;
+      return B2F_OK;
+    }
+  uint64_t table_bytes = 0;
+  fixed_base_plan_of(nullptr, nullptr, nullptr, &table_bytes);
+  b2f_fixed_base_tab* t = &ctx->fb_tab[ctx->fb_next++ % b2f_ctx::FB_TABS];
+  if (t == keep) t = &ctx->fb_tab[ctx->fb_next++ % b2f_ctx::FB_TABS];
+  t->live = false;
+  if (int rc = grow_device(ctx, &t->d, &t->cap, table_bytes, 1, s)) return rc;
+  t->curve = form >> 1;
+  memcpy(t->base, h_base, 64);
+  *tab = t;
+  *build = true;
+  return B2F_OK;
+}
+
+// what the transcript calls check alike: the state, the data block of n elements of elem bytes
+int transcript_check(b2f_ctx* ctx, const char* what, const uint64_t* d_state, const void* d_data, uint64_t n,
+                     uint64_t elem, uint32_t form) {
+  if (!d_state || !d_data) return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (((uintptr_t)d_state | (uintptr_t)d_data) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "%s: buffers must be 16-byte aligned", what);
+  if (form > B2F_FP_BN254_MONTGOMERY) return set_err(ctx, B2F_ERR_ARG, "%s: unknown form %u", what, form);
+  if (n == 0 || n > (1ull << 20))
+    return set_err(ctx, B2F_ERR_ARG, "%s: n %llu not in [1, 2^20]", what, (unsigned long long)n);
+  if (ranges_overlap(d_state, B2F_TRANSCRIPT_BYTES, d_data, n * elem))
+    return set_err(ctx, B2F_ERR_ARG, "%s: the state overlaps the data", what);
+  return B2F_OK;
+}
+}  // namespace
+
+extern "C" {
+
+B2F_API int b2f_transcript_init_dev(b2f_ctx* ctx, uint64_t* d_state, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "transcript init";
+  if (!d_state || ((uintptr_t)d_state & 15)) return set_err(ctx, B2F_ERR_ARG, "%s: d_state null or unaligned", what);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_transcript_init(d_state, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API int b2f_transcript_absorb_points_dev(b2f_ctx* ctx, uint64_t* d_state, const uint64_t* d_points, uint64_t n,
+                                             uint32_t form, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  if (int rc = transcript_check(ctx, "transcript absorb points", d_state, d_points, n, 64, form)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_transcript_absorb(d_state, d_points, (uint32_t)n, form, true, ctx->d_status + 2, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API int b2f_transcript_absorb_scalars_dev(b2f_ctx* ctx, uint64_t* d_state, const uint64_t* d_scalars, uint64_t n,
+                                              uint32_t form, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  if (int rc = transcript_check(ctx, "transcript absorb scalars", d_state, d_scalars, n, 32, form)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_transcript_absorb(d_state, d_scalars, (uint32_t)n, form, false, ctx->d_status + 2, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API int b2f_transcript_squeeze_dev(b2f_ctx* ctx, uint64_t* d_state, uint32_t form, uint64_t* d_challenge,
+                                       void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  if (int rc = transcript_check(ctx, "transcript squeeze", d_state, d_challenge, 1, 32, form)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  HIPCHK(ctx, launch_transcript_squeeze(d_state, form, d_challenge, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
+B2F_API int b2f_ipa_open_dev(b2f_ctx* ctx, uint64_t* d_p, uint64_t* d_b, uint64_t* d_g, uint64_t len,
+                             const uint64_t h_u_point[8], const uint64_t h_w_point[8], const uint64_t* d_z,
+                             const uint64_t* d_rand, uint64_t* d_state, uint32_t form, uint64_t* d_lr, uint64_t* d_u,
+                             uint64_t* d_cf, void* stream) {
+  if (!ctx) return B2F_ERR_ARG;
+  const char* what = "ipa open";
+  if (!h_u_point || !h_w_point || !d_z || !d_rand || !d_state || !d_lr || !d_u || !d_cf)
+    return set_err(ctx, B2F_ERR_ARG, "%s: null buffer", what);
+  if (((uintptr_t)d_z | (uintptr_t)d_rand | (uintptr_t)d_state | (uintptr_t)d_lr | (uintptr_t)d_u | (uintptr_t)d_cf) & 15)
+    return set_err(ctx, B2F_ERR_ARG, "%s: buffers must be 16-byte aligned", what);
+  if (int rc = ipa_check_vectors(ctx, what, d_p, d_b, d_g, len, form)) return rc;
+  uint64_t any_u = 0, any_w = 0;
+  for (int i = 0; i < 8; i++) {
+    any_u |= h_u_point[i];
+    any_w |= h_w_point[i];
+  }
+  if (!any_u || !any_w) return set_err(ctx, B2F_ERR_ARG, "%s: U or W is the identity", what);
+  uint32_t k = 0;
+  while ((1ull << k) < len) k++;
+  // every block the call touches: only the two read-only inputs may overlap each other
+  const struct {
+    const void* at;
+    uint64_t bytes;
+    bool written;
+  } blk[9] = {{d_p, 32 * len, true},       {d_b, 32 * len, true},    {d_g, 64 * len, true},
+              {d_z, 32, false},            {d_rand, 64ull * k, false}, {d_state, B2F_TRANSCRIPT_BYTES, true},
+              {d_lr, 128ull * k, true},    {d_u, 32ull * k, true},   {d_cf, 64, true}};
+  for (int i = 0; i < 9; i++)
+    for (int j = i + 1; j < 9; j++)
+      if ((blk[i].written || blk[j].written) && ranges_overlap(blk[i].at, blk[i].bytes, blk[j].at, blk[j].bytes))
+        return set_err(ctx, B2F_ERR_ARG, "%s: a buffer the call writes overlaps another", what);
+  uint64_t direct_max = 0;
+  if (!ipa_direct_for(&direct_max)) return set_err(ctx, B2F_ERR_ARG, "%s: the forced switch-over is malformed", what);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // scratch for the largest round, grown before anything is queued: the commitments' block, the
+  // rounds' block, and behind it the call's own words (raw L, R; values; the challenge)
+  size_t msm_need = 0;
+  for (uint64_t ln = len; ln >= 2; ln >>= 1) {
+    if (ln <= direct_max) continue;
+    MsmPlan plan;
+    if (!msm_plan_of(ln / 2, 2, 0, 0, &plan)) return set_err(ctx, B2F_ERR_ARG, "%s: no plan", what);
+    if (plan.scratch_bytes > msm_need) msm_need = plan.scratch_bytes;
+  }
+  const size_t own = ipa_scratch_bytes(len);
+  if (msm_need)
+    if (int rc = grow_device(ctx, &ctx->d_msm, &ctx->msm_cap, msm_need, 1, s)) return rc;
+  if (int rc = grow_device(ctx, &ctx->d_ipa, &ctx->ipa_cap, own + 512, 1, s)) return rc;
+  uint64_t* raw = reinterpret_cast<uint64_t*>((char*)ctx->d_ipa + own);  // 16 words
+  uint64_t *values = raw + 16, *chal = raw + 24;                          // 8 and 12 words
+  b2f_fixed_base_tab *tab_u = nullptr, *tab_w = nullptr;
+  bool build_u = false, build_w = false;
+  if (int rc = fixed_base_table_slot(ctx, h_u_point, form, nullptr, s, &tab_u, &build_u)) return rc;
+  const bool same = !memcmp(h_u_point, h_w_point, 64);
+  if (same) tab_w = tab_u;
+  else if (int rc = fixed_base_table_slot(ctx, h_w_point, form, tab_u, s, &tab_w, &build_w)) return rc;
+  int* sticky = ctx->d_status + 2;
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  if (build_u) {
+    HIPCHK(ctx, launch_fixed_base_table(h_u_point, form, (uint64_t*)tab_u->d, sticky, s));
+    tab_u->live = true;
+  }
+  if (build_w) {
+    HIPCHK(ctx, launch_fixed_base_table(h_w_point, form, (uint64_t*)tab_w->d, sticky, s));
+    tab_w->live = true;
+  }
+  uint32_t j = 0;
+  for (uint64_t ln = len; ln >= 2; ln >>= 1, j++) {
+    if (ln <= direct_max) {
+      HIPCHK(ctx, launch_ipa_round_direct(d_p, d_b, d_g, ln, form, raw, values, sticky, s));
+    } else {
+      MsmPlan plan;
+      if (!msm_plan_of(ln / 2, 2, 0, 0, &plan)) return set_err(ctx, B2F_ERR_ARG, "%s: no plan", what);
+      HIPCHK(ctx, launch_ipa_round_long(plan, d_p, d_b, d_g, ln, form, raw, values, ctx->d_msm, ctx->d_ipa, sticky, s));
+    }
+    HIPCHK(ctx, launch_fixed_base_blind(raw, values, d_z, d_rand + 8ull * j, form, (const uint64_t*)tab_u->d,
+                                        (const uint64_t*)tab_w->d, d_lr + 16ull * j, sticky, s));
+    HIPCHK(ctx, launch_ipa_challenge(d_lr + 16ull * j, d_rand + 8ull * j, d_state, form, d_u + 4ull * j, chal,
+                                     d_cf + 4, sticky, s));
+    HIPCHK(ctx, launch_ipa_fold_ptr(d_p, d_b, d_g, ln, chal, form, sticky, s));
+  }
+  HIPCHK(ctx, launch_ipa_finish(d_p, d_state, form, d_cf, s));
+  timed_end(ctx, tk, s);
+  return B2F_OK;
+}
+
 B2F_API int b2f_group_ntt_plan(uint32_t k, uint32_t form, uint64_t* scalar_muls, uint64_t* scratch_bytes) {
   if (k < 1 || k > 28 || form > B2F_FP_BN254_MONTGOMERY) return B2F_ERR_ARG;
   if (scalar_muls) *scalar_muls = group_ntt_scalar_muls(k);
@@ -1132,27 +1311,16 @@ B2F_API int b2f_fixed_base_mul_dev(b2f_ctx* ctx, const uint64_t h_base[8], const
     return set_err(ctx, B2F_ERR_ARG, "%s: len %llu not in [1, 2^28]", what, (unsigned long long)len);
   if (ranges_overlap(d_out, 64 * len, d_scalars, 32 * len))
     return set_err(ctx, B2F_ERR_ARG, "%s: the output overlaps the scalars", what);
-  uint64_t table_bytes = 0;
-  fixed_base_plan_of(nullptr, nullptr, nullptr, &table_bytes);
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // the table of this (curve, base): cached, or built into the next slot
   b2f_fixed_base_tab* tab = nullptr;
-  for (auto& t : ctx->fb_tab)
-    if (t.live && t.curve == (form >> 1) && !memcmp(t.base, h_base, 64)) tab = &t;
-  int tk = -1;
-  if (!tab) {
-    b2f_fixed_base_tab& t = ctx->fb_tab[ctx->fb_next++ % b2f_ctx::FB_TABS];
-    t.live = false;
-    if (int rc = grow_device(ctx, &t.d, &t.cap, table_bytes, 1, s)) return rc;
-    t.curve = form >> 1;
-    memcpy(t.base, h_base, 64);
-    tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
-    HIPCHK(ctx, launch_fixed_base_table(h_base, form, (uint64_t*)t.d, ctx->d_status + 2, s));
-    t.live = true;
-    tab = &t;
-  } else {
-    tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  bool build = false;
+  if (int rc = fixed_base_table_slot(ctx, h_base, form, nullptr, s, &tab, &build)) return rc;
+  int tk = timed_begin(ctx, B2F_KERNEL_QUOTIENT, s);
+  if (build) {
+    HIPCHK(ctx, launch_fixed_base_table(h_base, form, (uint64_t*)tab->d, ctx->d_status + 2, s));
+    tab->live = true;
   }
   HIPCHK(ctx, launch_fixed_base_mul(d_scalars, len, form, (const uint64_t*)tab->d, d_out, ctx->d_status + 2, s));
   timed_end(ctx, tk, s);

@@ -13,12 +13,14 @@
 //             kernel met a zero operand of an inverse (result zero, the inverse not called)
 // It allocates, copies, runs one lane per element on the null stream and synchronises.
 // B2F_ERR_ARG, nothing launched: a null pointer, n = 0 or n > 65,536, an unknown field or op,
-// an operand >= p, a zero `a` for an inverse (inv<F> does not terminate on 0 or on p).
+// an operand >= p (the wide reduction excepted: it takes any two 256-bit integers), a zero `a`
+// for an inverse (inv<F> does not terminate on 0 or on p).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/b2f.h"
 #include "b2f_field.h"
+#include "b2f_transcript.h"
 
 namespace b2f {
 namespace {
@@ -39,8 +41,12 @@ enum : uint32_t {
   B2F_FOP_INV_KALISKI = 10,
   B2F_FOP_INV_SAFEGCD = 11,
   B2F_FOP_INV_FERMAT = 12,
-  B2F_FOP_COUNT = 13
+  B2F_FOP_COUNT = 13,
+  // apart from the primitives above, whose operands are field elements: (a + b 2^256) mod p,
+  // canonical, of any two 256-bit integers (b2f_transcript.h: a challenge from a 64-byte digest)
+  B2F_FOP_REDUCE_WIDE = 32
 };
+__host__ __device__ inline bool is_inverse_op(uint32_t op) { return op >= B2F_FOP_INV && op <= B2F_FOP_INV_FERMAT; }
 
 template <class F>
 __global__ __launch_bounds__(64) void field_op_kernel(const uint64_t* a, const uint64_t* b, uint32_t n,
@@ -50,7 +56,7 @@ __global__ __launch_bounds__(64) void field_op_kernel(const uint64_t* a, const u
   const Fe x = load(a + 4ull * g), y = load(b + 4ull * g);
   Fe r = fe_zero();
   uint32_t flag = 1;
-  if (op >= B2F_FOP_INV && is_zero(x)) {  // the host refuses these; never reach inv<F> with 0
+  if (is_inverse_op(op) && is_zero(x)) {  // the host refuses these; never reach inv<F> with 0
     flag = 2;
   } else {
     switch (op) {
@@ -72,6 +78,7 @@ __global__ __launch_bounds__(64) void field_op_kernel(const uint64_t* a, const u
         break;
       }
       case B2F_FOP_INV_FERMAT: r = inv_fermat<F>(x); break;
+      case B2F_FOP_REDUCE_WIDE: r = transcript::reduce_wide<F>(x, y); break;
       default: flag = 0; break;
     }
   }
@@ -98,10 +105,10 @@ int classify(const uint64_t* x) {
 
 template <class F>
 int field_op(uint32_t op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, uint32_t* flags) {
-  for (size_t i = 0; i < n; i++) {
+  for (size_t i = 0; i < n && op != B2F_FOP_REDUCE_WIDE; i++) {
     const int ca = classify<F>(a + 4 * i), cb = classify<F>(b + 4 * i);
     if (ca == 2 || cb == 2) return B2F_ERR_ARG;
-    if (op >= B2F_FOP_INV && ca == 0) return B2F_ERR_ARG;
+    if (is_inverse_op(op) && ca == 0) return B2F_ERR_ARG;
   }
   const size_t bytes = 32 * n;
   uint64_t* d = nullptr;  // a | b | out | flags
@@ -130,7 +137,8 @@ int field_op(uint32_t op, const uint64_t* a, const uint64_t* b, size_t n, uint64
 
 extern "C" B2F_API int b2f_debug_field_op(uint32_t field, uint32_t op, const uint64_t* a, const uint64_t* b,
                                           size_t n, uint64_t* out, uint32_t* flags) {
-  if (!a || !b || !out || !flags || n == 0 || n > 65536 || field > 1 || op >= b2f::B2F_FOP_COUNT)
+  if (!a || !b || !out || !flags || n == 0 || n > 65536 || field > 1 ||
+      (op >= b2f::B2F_FOP_COUNT && op != b2f::B2F_FOP_REDUCE_WIDE))
     return B2F_ERR_ARG;
   return field ? b2f::field_op<b2f::field::Bn254>(op, a, b, n, out, flags)
                : b2f::field_op<b2f::field::Pallas>(op, a, b, n, out, flags);

@@ -108,6 +108,98 @@ __global__ __launch_bounds__(FB_THREADS) void fb_mul_kernel(const uint64_t* __re
   store_affine(out + 8 * i, r);
 }
 
+// The blinding of an IPA round's cross terms (b2f_ipa_open_dev), one workgroup:
+//   out[0] = L + [value_l z] U + [l_rand] W      out[1] = R + [value_r z] U + [r_rand] W
+// from the tables of U and W. Four multiples of 32 signed digits each: lane t holds digit t % 32 of
+// multiple t / 32 (0: value_l z on U, 1: l_rand on W, 2: value_r z on U, 3: r_rand on W), gathers
+// its one table entry, and the 64 lanes of an output are summed by a tree in LDS; the output's
+// first lane adds the round's raw point and converts to affine. No lane walks a doubling chain:
+// the depth is one gather, six additions and one inversion. values: (value_l, value_r) in the
+// form; z: canonical; rand: (l_rand, r_rand) in the form. An identity output raises B2F_ERR_FIELD
+// (halo2 refuses to write it to the transcript).
+constexpr uint32_t FB_BLIND_THREADS = 4 * FB_WINDOWS;
+struct BlindLds {
+  uint32_t w[FB_BLIND_THREADS][33];
+};
+template <class C, bool MONT>
+__global__ __launch_bounds__(FB_BLIND_THREADS) void fb_blind_kernel(
+    const uint64_t* __restrict__ lr_raw, const uint64_t* __restrict__ values, const uint64_t* __restrict__ z,
+    const uint64_t* __restrict__ rand, const uint64_t* __restrict__ table_u, const uint64_t* __restrict__ table_w,
+    uint64_t* __restrict__ out, int* sticky) {
+  using F = typename C::Base;
+  using FS = typename C::Scalar;
+  __shared__ BlindLds lds;
+  const uint32_t t = threadIdx.x, m = t / FB_WINDOWS, w = t % FB_WINDOWS, which = m >> 1;
+  Fe k;
+  if (m & 1u) {
+    k = load(rand + 4 * which);
+    if (MONT) k = to_canonical<FS>(k);
+  } else {
+    // mul(x, y) = x y / R: a Montgomery value against the canonical z is the canonical product; a
+    // canonical value gives it over R, which to_mont undoes
+    k = mul<FS>(load(values + 4 * which), load(z));
+    if (!MONT) k = to_mont<FS>(k);
+  }
+  // the recoding of fb_mul_kernel, kept up to this lane's window
+  uint32_t carry = 0, digit = 0;
+  bool negative = false;
+#pragma unroll 1
+  for (uint32_t q = 0; q <= w; q++) {
+    digit = (k.w[0] & 0xffu) + carry;
+#pragma unroll
+    for (int i = 0; i < 7; i++) k.w[i] = (k.w[i] >> 8) | (k.w[i + 1] << 24);
+    k.w[7] >>= 8;
+    negative = digit > FB_HALF;
+    carry = negative ? 1u : 0u;
+    if (negative) digit = 256u - digit;
+  }
+  Xyzz acc = xyzz_identity();
+  if (digit != 0) {  // 1 <= digit <= 128, w < 32: inside the table for any 256-bit scalar
+    Affine p = load_affine(((m & 1u) ? table_w : table_u) + 8ull * (w * FB_HALF + (digit - 1)));
+    if (negative) p = neg<F>(p);
+    acc = from_affine<F>(p);
+  }
+  auto put = [&](uint32_t at, const Xyzz& v) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      lds.w[at][i] = v.x.w[i];
+      lds.w[at][8 + i] = v.y.w[i];
+      lds.w[at][16 + i] = v.zz.w[i];
+      lds.w[at][24 + i] = v.zzz.w[i];
+    }
+  };
+  auto get = [&](uint32_t at) {
+    Xyzz v;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      v.x.w[i] = lds.w[at][i];
+      v.y.w[i] = lds.w[at][8 + i];
+      v.zz.w[i] = lds.w[at][16 + i];
+      v.zzz.w[i] = lds.w[at][24 + i];
+    }
+    return v;
+  };
+  put(t, acc);
+  __syncthreads();
+  const uint32_t lane = t & (2 * FB_WINDOWS - 1);  // within the output's 64 lanes
+#pragma unroll 1
+  for (uint32_t s = FB_WINDOWS; s > 0; s >>= 1) {
+    if (lane < s) {
+      acc = add<F>(acc, get(t + s));
+      put(t, acc);
+    }
+    __syncthreads();
+  }
+  if (lane == 0) {
+    acc = madd<F>(acc, load_affine(lr_raw + 8ull * which));
+    bool ok = true;
+    const Affine r = to_affine<F>(acc, ok);
+    if (!ok) atomicOr(sticky, 1 << B2F_ERR_CHECK);
+    if (is_identity(r)) atomicOr(sticky, 1 << B2F_ERR_FIELD);
+    store_affine(out + 8ull * which, r);
+  }
+}
+
 }  // namespace
 
 void fixed_base_plan_of(uint32_t* window_bits, uint32_t* windows, uint64_t* table_points, uint64_t* table_bytes) {
@@ -135,6 +227,16 @@ hipError_t launch_fixed_base_mul(const uint64_t* d_scalars, uint64_t len, uint32
   with_curve_form(form, [&](auto c, auto mont) {
     hipLaunchKernelGGL((fb_mul_kernel<decltype(c), decltype(mont)::value>), grid, block, 0, s, d_scalars, len,
                        d_table, d_out, sticky);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_fixed_base_blind(const uint64_t* d_lr_raw, const uint64_t* d_values, const uint64_t* d_z,
+                                   const uint64_t* d_rand, uint32_t form, const uint64_t* d_table_u,
+                                   const uint64_t* d_table_w, uint64_t* d_out, int* sticky, hipStream_t s) {
+  with_curve_form(form, [&](auto c, auto mont) {
+    hipLaunchKernelGGL((fb_blind_kernel<decltype(c), decltype(mont)::value>), dim3(1), dim3(FB_BLIND_THREADS), 0, s,
+                       d_lr_raw, d_values, d_z, d_rand, d_table_u, d_table_w, d_out, sticky);
   });
   return hipGetLastError();
 }

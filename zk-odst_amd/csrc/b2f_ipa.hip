@@ -6,9 +6,13 @@
 //          value_l = <p[half..], b[..half]>   value_r = <p[..half], b[half..]>   (field)
 //   fold   p[i] += p[half+i] u^-1   b[i] += b[half+i] u   G[i] = affine(G[i] + [u] G[half+i])
 //
-// The transcript, the blinding and the U / W terms are the caller's; every challenge is a host
-// argument. Forms 0/1 are Vesta, 2/3 BN254 G1 (b2f_curve.h); scalars are in `form`, points in
-// base-field Montgomery form.
+// For the three separate calls the transcript, the blinding and the U / W terms are the caller's and
+// every challenge is a host argument. b2f_ipa_open_dev queues the whole loop:
+// per round the same round launches, the blinding of L and R from the tables of U and W
+// (b2f_fixed_base.hip), ipa_challenge_kernel (absorb L_j, R_j; squeeze u_j; u_j^-1; f) on the
+// device transcript of b2f_transcript.h, and the fold kernels' entries that read u_j from memory;
+// then ipa_finish_kernel (c, and c and f absorbed). Forms 0/1 are Vesta, 2/3 BN254 G1
+// (b2f_curve.h); scalars are in `form`, points in base-field Montgomery form.
 //
 // Cross terms: a long round views p as a block of two columns of `half` rows, column 0 against
 // G[half..] (R) and column 1 against G[..half] (L), and runs ONE Pippenger pass of b2f_msm.hip with
@@ -31,6 +35,7 @@
 #include "b2f_curve.h"
 #include "b2f_field.h"
 #include "b2f_launch.h"
+#include "b2f_transcript.h"
 
 namespace b2f {
 
@@ -218,28 +223,41 @@ __global__ __launch_bounds__(IPA_THREADS) void ipa_combine_kernel(const uint64_t
 }
 
 // ---- the folds ------------------------------------------------------------------------------------
+// Each fold kernel has two entries over one body: the multipliers as kernel arguments (the host's
+// challenge, b2f_ipa_fold_dev) or read from device memory where the challenge kernel left them
+// (b2f_ipa_open_dev: chal[0..3] = u canonical, [4..7] = u Montgomery, [8..11] = u^-1 Montgomery).
 // p[i] += p[half + i] u^-1, b[i] += b[half + i] u: lane i touches rows i and half + i only
 template <class FS>
-__global__ __launch_bounds__(IPA_THREADS) void ipa_fold_scalars_kernel(uint64_t* __restrict__ p,
-                                                                       uint64_t* __restrict__ b, uint32_t half,
-                                                                       const Words4 u_mont, const Words4 uinv_mont) {
+__device__ __forceinline__ void fold_scalars_body(uint64_t* __restrict__ p, uint64_t* __restrict__ b, uint32_t half,
+                                                  const Fe& u_mont, const Fe& uinv_mont) {
   const uint32_t i = blockIdx.x * IPA_THREADS + threadIdx.x;
   if (i >= half) return;
   const Fe plo = load(p + 4ull * i), phi = load(p + 4ull * (half + i));
   const Fe blo = load(b + 4ull * i), bhi = load(b + 4ull * (half + i));
-  store(p + 4ull * i, add<FS>(plo, mul<FS>(phi, load_words(uinv_mont.v))));
-  store(b + 4ull * i, add<FS>(blo, mul<FS>(bhi, load_words(u_mont.v))));
+  store(p + 4ull * i, add<FS>(plo, mul<FS>(phi, uinv_mont)));
+  store(b + 4ull * i, add<FS>(blo, mul<FS>(bhi, u_mont)));
+}
+template <class FS>
+__global__ __launch_bounds__(IPA_THREADS) void ipa_fold_scalars_kernel(uint64_t* __restrict__ p,
+                                                                       uint64_t* __restrict__ b, uint32_t half,
+                                                                       const Words4 u_mont, const Words4 uinv_mont) {
+  fold_scalars_body<FS>(p, b, half, load_words(u_mont.v), load_words(uinv_mont.v));
+}
+template <class FS>
+__global__ __launch_bounds__(IPA_THREADS) void ipa_fold_scalars_ptr_kernel(uint64_t* __restrict__ p,
+                                                                           uint64_t* __restrict__ b, uint32_t half,
+                                                                           const uint64_t* __restrict__ chal) {
+  fold_scalars_body<FS>(p, b, half, load(chal + 4), load(chal + 8));
 }
 
 // G[i] = affine(G[i] + [u] G[half + i]): one lane per point, u (canonical) the same for the wave
 template <class C>
-__global__ __launch_bounds__(COLLAPSE_THREADS) void ipa_collapse_kernel(uint64_t* __restrict__ g, uint32_t half,
-                                                                        const Words4 u, int* sticky) {
+__device__ __forceinline__ void collapse_body(uint64_t* __restrict__ g, uint32_t half, const Fe& u, int* sticky) {
   using F = typename C::Base;
   const uint32_t i = blockIdx.x * COLLAPSE_THREADS + threadIdx.x;
   if (i >= half) return;
   const Affine lo = load_affine(g + 8ull * i);
-  Xyzz acc = scalar_mul<F>(load_affine(g + 8ull * (half + i)), load_words(u.v));
+  Xyzz acc = scalar_mul<F>(load_affine(g + 8ull * (half + i)), u);
   acc = madd<F>(acc, lo);
   bool ok = true;
 #ifdef B2F_IPA_NO_AFFINE  // ablation builds only (tools/bench_ipa.py): the collapse without its inversion
@@ -251,6 +269,85 @@ __global__ __launch_bounds__(COLLAPSE_THREADS) void ipa_collapse_kernel(uint64_t
 #endif
   if (!ok) atomicOr(sticky, 1 << B2F_ERR_CHECK);
   store_affine(g + 8ull * i, a);
+}
+template <class C>
+__global__ __launch_bounds__(COLLAPSE_THREADS) void ipa_collapse_kernel(uint64_t* __restrict__ g, uint32_t half,
+                                                                        const Words4 u, int* sticky) {
+  collapse_body<C>(g, half, load_words(u.v), sticky);
+}
+// u from memory: every lane reads the same words and the first lane's copy is taken, so the
+// scalar is wave-uniform for the compiler too and scalar_mul's branches stay uniform
+template <class C>
+__global__ __launch_bounds__(COLLAPSE_THREADS) void ipa_collapse_ptr_kernel(uint64_t* __restrict__ g, uint32_t half,
+                                                                            const uint64_t* __restrict__ chal,
+                                                                            int* sticky) {
+  Fe u = load(chal);
+#pragma unroll
+  for (int i = 0; i < 8; i++) u.w[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)u.w[i]);
+  collapse_body<C>(g, half, u, sticky);
+}
+
+// ---- the challenge of a round of the one-call opening ------------------------------------------------
+// One workgroup of one wave. lr: the blinded (L_j, R_j), affine; four lanes convert the four
+// coordinates to their canonical bytes, then lane 0 absorbs the two points, squeezes u_j, inverts
+// it and moves f on:  f += l_rand u^-1 + r_rand u  (f and rand in the form). u goes to out_u
+// (canonical) and, with its Montgomery form and inverse, to chal for the folds. u = 0 raises
+// B2F_ERR_FIELD (halo2 would fail to invert it); its inverse is then written as zero.
+template <class C, bool MONT>
+__global__ __launch_bounds__(64) void ipa_challenge_kernel(const uint64_t* __restrict__ lr,
+                                                           const uint64_t* __restrict__ rand,
+                                                           uint64_t* __restrict__ state, uint64_t* __restrict__ out_u,
+                                                           uint64_t* __restrict__ chal, uint64_t* __restrict__ f,
+                                                           int* sticky) {
+  using FS = typename C::Scalar;
+  __shared__ transcript::State st;
+  __shared__ uint8_t bytes[130];
+  const uint32_t t = threadIdx.x;
+  if (t < 4) {
+    const Fe c = to_canonical<typename C::Base>(load(lr + 4 * t));
+    transcript::put_bytes(bytes + 65 * (t >> 1) + 1 + 32 * (t & 1u), c);
+    if (!(t & 1u)) bytes[65 * (t >> 1)] = 1;
+  }
+  __syncthreads();
+  if (t != 0) return;
+  transcript::tr_load(st, state);
+  transcript::tr_absorb(st, bytes, 130);
+  const Fe u = transcript::tr_squeeze<FS>(st);
+  transcript::tr_store(st, state);
+  const Fe u_mont = to_mont<FS>(u);
+  bool ok = true;
+  Fe uinv_mont = fe_zero();
+  if (is_zero(u)) atomicOr(sticky, 1 << B2F_ERR_FIELD);
+  else uinv_mont = inv_safegcd<FS>(u_mont, ok);
+  if (!ok) atomicOr(sticky, 1 << B2F_ERR_CHECK);
+  Fe fm = load(f), l = load(rand), r = load(rand + 4);
+  if (!MONT) {
+    fm = to_mont<FS>(fm);
+    l = to_mont<FS>(l);
+    r = to_mont<FS>(r);
+  }
+  fm = add<FS>(fm, add<FS>(mul<FS>(l, uinv_mont), mul<FS>(r, u_mont)));
+  if (!MONT) fm = to_canonical<FS>(fm);
+  store(f, fm);
+  store(out_u, u);
+  store(chal, u);
+  store(chal + 4, u_mont);
+  store(chal + 8, uinv_mont);
+}
+
+// After the last round: c = p[0] to cf[0..3], and c then f (cf[4..7]) absorbed as scalars.
+template <class FS, bool MONT>
+__global__ __launch_bounds__(64) void ipa_finish_kernel(const uint64_t* __restrict__ p, uint64_t* __restrict__ state,
+                                                        uint64_t* __restrict__ cf) {
+  __shared__ transcript::State st;
+  __shared__ uint8_t stage[33];
+  if (threadIdx.x != 0) return;
+  const Fe c = load(p), f = load(cf + 4);
+  transcript::tr_load(st, state);
+  transcript::tr_absorb_scalar(st, stage, MONT ? to_canonical<FS>(c) : c);
+  transcript::tr_absorb_scalar(st, stage, MONT ? to_canonical<FS>(f) : f);
+  transcript::tr_store(st, state);
+  store(cf, c);
 }
 
 }  // namespace
@@ -315,6 +412,41 @@ hipError_t launch_ipa_fold(uint64_t* d_p, uint64_t* d_b, uint64_t* d_g, uint64_t
     hipLaunchKernelGGL((ipa_collapse_kernel<decltype(c)>), dim3((half + COLLAPSE_THREADS - 1) / COLLAPSE_THREADS),
                        dim3(COLLAPSE_THREADS), 0, s, d_g, half, words4(u), sticky);
     return 0;
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_ipa_fold_ptr(uint64_t* d_p, uint64_t* d_b, uint64_t* d_g, uint64_t len, const uint64_t* d_chal,
+                               uint32_t form, int* sticky, hipStream_t s) {
+  const uint32_t half = (uint32_t)(len / 2);
+  with_field(form, [&](auto f) {
+    hipLaunchKernelGGL((ipa_fold_scalars_ptr_kernel<decltype(f)>), dim3((half + IPA_THREADS - 1) / IPA_THREADS),
+                       dim3(IPA_THREADS), 0, s, d_p, d_b, half, d_chal);
+    return 0;
+  });
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  with_curve(form, [&](auto c) {
+    hipLaunchKernelGGL((ipa_collapse_ptr_kernel<decltype(c)>), dim3((half + COLLAPSE_THREADS - 1) / COLLAPSE_THREADS),
+                       dim3(COLLAPSE_THREADS), 0, s, d_g, half, d_chal, sticky);
+    return 0;
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_ipa_challenge(const uint64_t* d_lr, const uint64_t* d_rand, uint64_t* d_state, uint32_t form,
+                                uint64_t* d_u, uint64_t* d_chal, uint64_t* d_f, int* sticky, hipStream_t s) {
+  with_curve_form(form, [&](auto c, auto mont) {
+    hipLaunchKernelGGL((ipa_challenge_kernel<decltype(c), decltype(mont)::value>), dim3(1), dim3(64), 0, s, d_lr,
+                       d_rand, d_state, d_u, d_chal, d_f, sticky);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_ipa_finish(const uint64_t* d_p, uint64_t* d_state, uint32_t form, uint64_t* d_cf, hipStream_t s) {
+  with_form(form, [&](auto f, auto mont) {
+    hipLaunchKernelGGL((ipa_finish_kernel<decltype(f), decltype(mont)::value>), dim3(1), dim3(64), 0, s, d_p, d_state,
+                       d_cf);
   });
   return hipGetLastError();
 }

@@ -161,6 +161,16 @@ hipError_t launch_ipa_round_long(const MsmPlan& plan, const uint64_t* d_p, const
 hipError_t launch_ipa_fold(uint64_t* d_p, uint64_t* d_b, uint64_t* d_g, uint64_t len, const uint64_t* u,
                            const uint64_t* u_mont, const uint64_t* uinv_mont, uint32_t form, int* sticky,
                            hipStream_t s);
+// The one-call opening's steps. launch_ipa_challenge: absorb the blinded (L_j, R_j) at d_lr, squeeze u_j to
+// d_u (canonical), move f on (d_f, in the form, with d_rand = (l_rand_j, r_rand_j)) and leave u, its
+// Montgomery form and its inverse's in the 12 words at d_chal, which launch_ipa_fold_ptr's kernels
+// read where launch_ipa_fold's take kernel arguments. launch_ipa_finish: c = p[0] to d_cf[0..3], c and
+// f (d_cf[4..7]) absorbed as scalars.
+hipError_t launch_ipa_fold_ptr(uint64_t* d_p, uint64_t* d_b, uint64_t* d_g, uint64_t len, const uint64_t* d_chal,
+                               uint32_t form, int* sticky, hipStream_t s);
+hipError_t launch_ipa_challenge(const uint64_t* d_lr, const uint64_t* d_rand, uint64_t* d_state, uint32_t form,
+                                uint64_t* d_u, uint64_t* d_chal, uint64_t* d_f, int* sticky, hipStream_t s);
+hipError_t launch_ipa_finish(const uint64_t* d_p, uint64_t* d_state, uint32_t form, uint64_t* d_cf, hipStream_t s);
 #ifdef B2F_DIAG
 int diag_ipa_direct(uint64_t* len);
 #endif
@@ -184,6 +194,22 @@ hipError_t launch_fixed_base_table(const uint64_t* base, uint32_t form, uint64_t
                                    hipStream_t s);
 hipError_t launch_fixed_base_mul(const uint64_t* d_scalars, uint64_t len, uint32_t form, const uint64_t* d_table,
                                  uint64_t* d_out, int* sticky, hipStream_t s);
+
+// The blinded cross terms of an IPA round from the tables of U and W (b2f_ipa_open_dev):
+// d_out[0..7] = L + [value_l z] U + [l_rand] W, d_out[8..15] the same for R. d_lr_raw: the round's (L, R);
+// d_values: (value_l, value_r) and d_rand: (l_rand, r_rand), in the form; d_z: canonical. An identity
+// output raises B2F_ERR_FIELD in sticky.
+hipError_t launch_fixed_base_blind(const uint64_t* d_lr_raw, const uint64_t* d_values, const uint64_t* d_z,
+                                   const uint64_t* d_rand, uint32_t form, const uint64_t* d_table_u,
+                                   const uint64_t* d_table_w, uint64_t* d_out, int* sticky, hipStream_t s);
+
+// b2f_transcript.hip: the Fiat-Shamir transcript on a 32-word device state. points: d_data holds n
+// affine points (64 bytes, base-field Montgomery), else n scalars in `form`. The identity point raises
+// B2F_ERR_FIELD in sticky. The challenge is four canonical limbs of the form's scalar field.
+hipError_t launch_transcript_init(uint64_t* d_state, hipStream_t s);
+hipError_t launch_transcript_absorb(uint64_t* d_state, const uint64_t* d_data, uint32_t n, uint32_t form,
+                                    bool points, int* sticky, hipStream_t s);
+hipError_t launch_transcript_squeeze(uint64_t* d_state, uint32_t form, uint64_t* d_challenge, hipStream_t s);
 
 // b2f_export.hip
 hipError_t launch_export_fp(const uint32_t* d_advice, uint64_t total_rows, uint64_t row_begin,
